@@ -2,6 +2,11 @@
 """Benchmark of the MI355X batched NMPC solve path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg5] [--batch B] [--horizon N]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+line with the headline figure.  Everything else described below -- `value_solve_only`, `roofline`, `secondary`,
+`tolerance_sweep`, `exact_hessian`, `cpu_baseline` -- is measured only with --full.
 
 One "step" = one cold-started batched SQP solve of B independent instances per GPU (cfg#2: 2-link arm, nx=4,
 nu=2, N=30, h=2 ms, fp64), i.e. what the reference does per control tick in ModelControl::calc_u
@@ -83,6 +88,14 @@ def parse(argv=None):
     ap.add_argument("--kkt", choices=["auto", "condensed", "riccati", "group"], default="auto",
                     help="KKT solver (mmpc_opts.kkt_solver); auto = the library's choice")
     ap.add_argument("--horizon", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the solve-only loop with the roofline, "
+                         "the cfg#3 / cfg#5 'secondary' lines, the tolerance sweeps, the exact-Hessian comparison and "
+                         "the CPU baseline (each can still be switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (V, u0, status, iters of "
+                         "this rank's instances) as DIR/<name>.npy in float64; above 64 MB a fixed seeded sample of "
+                         "the instances, their row numbers in DIR/rows.npy")
     ap.add_argument("--tol", type=float, default=None,
                     help="outer tolerance: tol_grad = tol, tol_defect = tol/100 (default: 1e-8 / 1e-10)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0,
@@ -231,6 +244,27 @@ def lib_sha256(path: str) -> str:
     return hsh.hexdigest()
 
 
+DUMP_BUDGET = 64_000_000   # --dump-outputs: bytes in all
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: `arrays` (name -> array with one row per instance) as <dirname>/<name><suffix>.npy in float64.
+    Above DUMP_BUDGET bytes in all, the same seeded sample of rows of every array (sorted; a function of SEED and
+    the row count alone) and the sampled row numbers as rows<suffix>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(8 * (a.size // max(rows, 1)) for a in arrays.values())
+    header = 256 * (len(arrays) + 1)   # .npy headers (128 bytes each for these shapes), with room to spare
+    keep = None
+    if rows * row_bytes + header > DUMP_BUDGET:
+        m = (DUMP_BUDGET - header) // (row_bytes + 8)
+        keep = np.sort(np.random.default_rng(SEED).choice(rows, size=m, replace=False))
+        np.save(os.path.join(dirname, f"rows{suffix}.npy"), keep.astype(np.float64))
+    for name, a in arrays.items():
+        a = a if keep is None else a[keep]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 # ------------------------------------------------------------------ test stand-in (no GPU)
 class _StandInSolver:
     """--standin only: a CPU 'solver' with the mmpc.Solver call shape whose outputs are a fixed function of the
@@ -283,9 +317,9 @@ def run_rank(args):
     if pg:
         import mmpc.dist as mdist
         out["process_group"] = mdist.rccl_info()
-    # the default (headline) invocation also measures the exo workloads of SURVEY.md 8d inside the same run, so the
-    # driver's clock covers them: cfg#3 (at N > 1 ranks: cfg#4, weak-scaled 65536 instances per GPU) and cfg#5
-    if args.config == "cfg2" and not args.no_secondary and not args.standin and args.batch is None \
+    # --full: the default (headline) configuration also measures the exo workloads of SURVEY.md 8d inside the same
+    # run: cfg#3 (at N > 1 ranks: cfg#4, weak-scaled 65536 instances per GPU) and cfg#5
+    if args.full and args.config == "cfg2" and not args.no_secondary and not args.standin and args.batch is None \
             and args.horizon is None:
         out["secondary"] = {c: run_config(args, c, world, rank, primary=False) for c in ("cfg3", "cfg5")}
     if rank == 0:
@@ -447,24 +481,34 @@ def run_config(args, name, world, rank, primary=True):
     elapsed = time.perf_counter() - t0
     step_ms = ev[0].elapsed_time(ev[1]) / args.steps if ev else 0.0   # generation + solve, per step
     elapsed = mdist.max_over_ranks(elapsed, device=dev)
-    # the same K solves again on the resident inputs of the last step (block 0), without the generation: the
-    # solve-only rate beside the line's value, and the solve kernel's own mean duration for the roofline
-    if coll:
-        dist.barrier()
-    sync()
-    t1 = time.perf_counter()
-    if ev:
-        ev[0].record(stream)
-    for k in range(args.steps):
-        solve(k, args.steps - 1)
-        if ev and k == args.steps - 1:
-            ev[1].record(stream)
-        results_to_host(k, args.steps - 1)
-    sync()
-    if coll:
-        dist.barrier()
-    elapsed_solve = mdist.max_over_ranks(time.perf_counter() - t1, device=dev)
-    kern_ms = ev[0].elapsed_time(ev[1]) / args.steps if ev else 0.0
+    if args.dump_outputs and primary:   # what the last timed step handed to its caller, this rank's instances
+        last = args.steps - 1
+        if zc(last, last):
+            u0_l, st_l, it_l = (a.copy() for a in hviews[last % 2])
+        else:
+            u0_l, st_l, it_l = u0.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
+        dump_outputs(args.dump_outputs, {"V": V.cpu().numpy(), "u0": u0_l.reshape(Bc, nu)[:n], "status": st_l[:n],
+                                         "iters": it_l[:n]}, suffix=f"_rank{rank}" if world > 1 else "")
+    elapsed_solve = kern_ms = None
+    if args.full:
+        # the same K solves again on the resident inputs of the last step (block 0), without the generation: the
+        # solve-only rate beside the line's value, and the solve kernel's own mean duration for the roofline
+        if coll:
+            dist.barrier()
+        sync()
+        t1 = time.perf_counter()
+        if ev:
+            ev[0].record(stream)
+        for k in range(args.steps):
+            solve(k, args.steps - 1)
+            if ev and k == args.steps - 1:
+                ev[1].record(stream)
+            results_to_host(k, args.steps - 1)
+        sync()
+        if coll:
+            dist.barrier()
+        elapsed_solve = mdist.max_over_ranks(time.perf_counter() - t1, device=dev)
+        kern_ms = ev[0].elapsed_time(ev[1]) / args.steps if ev else 0.0
 
     def hbytes(k):
         return torch.from_numpy(np.frombuffer(hbuf[k % 2]._buf, dtype=np.uint8).copy())
@@ -505,8 +549,6 @@ def run_config(args, name, world, rank, primary=True):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "value_solve_only": total / elapsed_solve,
-        "ms_per_step_solve_only": elapsed_solve / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None,
@@ -534,7 +576,7 @@ def run_config(args, name, world, rank, primary=True):
                                     "the per-tick input packing) + cold-start solve + results (u_0*, status, iters) "
                                     "on the host"
                                     + ("; the last step's table of all ranks on rank 0's host" if coll else "")
-                                    + "; value_solve_only: the same K solves on resident inputs")},
+                                    + ("; value_solve_only: the same K solves on resident inputs" if args.full else ""))},
         "converged": conv,
         "gathered_results_match": ok,
         "zero_copy_results_checked": zc_ok is not None,
@@ -550,22 +592,27 @@ def run_config(args, name, world, rank, primary=True):
                                            for v in tail[r * nbytes:r * nbytes + Bc * nu * 8].view(torch.float64)
                                            .view(Bc, nu)[:nrows[r], 0].tolist()]
     else:
-        out["kernel_ms"] = kern_ms
         out["step_gpu_ms"] = step_ms   # generation + solve kernels of one step (HIP events)
-        out["roofline"] = roofline(args, name, cfg, mmpc, solver, ksolver, N, nx, nu, n, iters, kern_ms, hess)
-    if name == "cfg5" and world == 1 and not standin and not args.no_sweep:
+    if args.full:
+        out["value_solve_only"] = total / elapsed_solve
+        out["ms_per_step_solve_only"] = elapsed_solve / args.steps * 1e3
+        if not standin:
+            out["kernel_ms"] = kern_ms
+            out["roofline"] = roofline(args, name, cfg, mmpc, solver, ksolver, N, nx, nu, n, iters, kern_ms, hess)
+    sweep = args.full and world == 1 and not standin and not args.no_sweep
+    if name == "cfg5" and sweep:
         out["tolerance_sweep"] = cfg5_sweep(path, cfg, n, x0, up, tr, w, args.hessian)
-    if (name == "cfg2" and primary and world == 1 and not standin and not args.no_sweep and args.u_bound is None
+    if (name == "cfg2" and primary and sweep and args.u_bound is None
             and args.x_bound is None and args.tol is None and args.kkt == "auto" and args.hessian == "auto"):
         out["tolerance_sweep"] = cfg5_sweep(path, cfg, n, x0, up, tr, w, args.hessian, fp32=False)
-    if (name == "cfg3" and world == 1 and not standin and not args.no_sweep and args.tol is None
+    if (name == "cfg3" and sweep and args.tol is None
             and (not primary or (args.u_bound is None and args.x_bound is None and args.kkt == "auto"
                                  and args.hessian == "auto"))):
         # the exo solve at the reference's IPOPT tolerance (ModelControl.cpp:54) beside the line's 1e-8 / 1e-10
         out["tolerance_sweep"] = cfg5_sweep(path, cfg, n, x0, up, tr, w, "auto", fp32=False)
         # and with IPOPT's exact Hessian (the line runs Gauss-Newton, the exo's AUTO choice): iteration histograms
         out["exact_hessian"] = hessian_compare(path, n, x0, up, tr, w, V, iters)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not standin and name != "cfg5":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not standin and name != "cfg5":
         out["cpu_baseline"] = cpu_baseline(cfg, N, h, args.cpu_seconds, V.cpu().numpy(), iters, tol_grad,
                                            tol_defect, hess, None if ulb is None else args.u_bound,
                                            args.x_bound if primary else None, ksolver)

@@ -49,7 +49,14 @@ def build_mass():
     return M
 
 
-MASS = build_mass()
+_MASS = None
+
+
+def MASS(qv):  # built on first use: importing this module (tests use synth_exo) does not read the reference
+    global _MASS
+    if _MASS is None:
+        _MASS = build_mass()
+    return _MASS(qv)
 
 
 def f(x, u):

@@ -16,7 +16,7 @@ for cfg in ${CONFIGS:-cfg2}; do
     for v in ${VARIANTS:-prev cur}; do
       if [ "$v" = cur ]; then unset MMPC_LIB_PATH; else export MMPC_LIB_PATH=$PWD/lib_var/$v/libmmpc.so; fi
       f="$OUT/b_${v}_${cfg}_${rep}.json"
-      timeout -k 10 200 python bench.py --config "$cfg" ${BENCH_ARGS:-} --steps 20 --warmup 3 --no-cpu-baseline \
+      timeout -k 10 200 python bench.py --full --config "$cfg" ${BENCH_ARGS:-} --steps 20 --warmup 3 --no-cpu-baseline \
         --no-secondary --no-sweep > "$f" 2> "$OUT/b_${v}.err" || { tail -5 "$OUT/b_${v}.err"; exit 1; }
       python3 -c "import json; d=json.load(open('$f')); print('$cfg $v', round(d['value']), round(d['kernel_ms'], 5), d['mean_sqp_iters'], d['max_sqp_iters'], d['converged'])"
     done

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for v in ${VARIANTS:-a b}; do
   export MMPC_LIB_PATH=$PWD/lib_var/$v/libmmpc.so
   for rep in 1 2; do
-    timeout -k 10 200 python bench.py ${BENCH_ARGS:-} --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_$v.$rep.json" 2> "$OUT/bench_$v.err" || { tail -5 "$OUT/bench_$v.err"; exit 1; }
+    timeout -k 10 200 python bench.py --full ${BENCH_ARGS:-} --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_$v.$rep.json" 2> "$OUT/bench_$v.err" || { tail -5 "$OUT/bench_$v.err"; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/bench_$v.$rep.json')); print('$v', d['value'], d['ms_per_step'], d['kernel_ms'], d['mean_sqp_iters'], d['converged'])"
   done
 done

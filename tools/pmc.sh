@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {  # name, rocprofv3 options...
   local name=$1; shift
-  timeout -s KILL 120 rocprofv3 --kernel-trace "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py ${BENCH_ARGS:-} --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sweep > "$OUT/$name.log" 2>&1 || { echo "pass $name failed"; tail -5 "$OUT/$name.log"; return 1; }
+  timeout -s KILL 120 rocprofv3 --kernel-trace "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py --full ${BENCH_ARGS:-} --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sweep > "$OUT/$name.log" 2>&1 || { echo "pass $name failed"; tail -5 "$OUT/$name.log"; return 1; }
 }
 timeout -s KILL 60 rocprofv3 -L > "$OUT/counters.txt" 2>&1 || true
 have() { grep -qw "$1" "$OUT/counters.txt"; }
