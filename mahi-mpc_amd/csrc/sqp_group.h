@@ -11,8 +11,10 @@
 // Group reductions (J, |c|_1, max|c|, merit) are 16-lane butterflies; the NLP, merit, line search and stop test
 // are those of sqp_wave.h / sqp_lane.h / oracle.  B = 4096 gives 1024 waves = one per SIMD.
 //
-// LDS per instance (fp64): x_k, u_k, F_k, c_k, hFq_k, hFqd_k, hFu_k, d_k, dx_k, du_k (cross-lane data); the
-// targets stay in HBM (read-only) and the gains K_k in a per-instance HBM workspace (serial lane only).
+// LDS per instance (fp64): x_k, u_k, d_k (then lam_k), dx_k, du_k, F_k, c_k, hFq_k, hFqd_k, hFu_k, the targets r_k
+// (cross-lane data).  The gains K_k | kff_k go through a per-instance HBM workspace.  The exact-Hessian blocks W_k go
+// there too, except in the unbounded solve of a model with a packed W record (WPack; the 2-link arm, cfg#2): its
+// records stay in LDS, over d / lam, dx and du, which are dead from the W pass to the step sweep.
 #pragma once
 #include <type_traits>
 
@@ -28,32 +30,50 @@ namespace mmpc {
 #ifndef MMPC_GROUP_XB_PAIRS
 #define MMPC_GROUP_XB_PAIRS 1
 #endif
-// A/B switch (round 6, diagnostic builds): the W_k and [K_k | kff_k] records go to the HBM workspace with
-// non-temporal stores (no L2 allocation) instead of plain ones
 #ifndef MMPC_GROUP_EXIT_HOLD   // resident finish of the 16-lane kernel; 0: waves exit as they finish
 #define MMPC_GROUP_EXIT_HOLD 0
-#endif
-#ifndef MMPC_GROUP_WZERO_ONCE   // W_k's structural zeros stored once per launch (w_struct_zero)
-#define MMPC_GROUP_WZERO_ONCE 1
 #endif
 #ifndef MMPC_GROUP_WB_COALESCED   // A/B switch: V written back 16 consecutive doubles per store instruction
 #define MMPC_GROUP_WB_COALESCED 0
 #endif
-#ifndef MMPC_GROUP_NT_STORES
-#define MMPC_GROUP_NT_STORES 0
-#endif
-template <class T>
-__device__ __forceinline__ void ws_store(T* p, T v) {
-    if constexpr (MMPC_GROUP_NT_STORES) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-// Entries of W_k's x rows that Model::eval_hess always leaves 0 (structural zeros): a launch stores them in its first
-// W pass only (MMPC_GROUP_WZERO_ONCE, round 6).  2-link arm (two_link_fast.h eval_hess: q_A enters only through
-// gravity, the torques linearly): row 0 is zero in columns 2..5, rows 2 and 3 in columns 0, 4 and 5.
+// Entries of W_k's x rows that Model::eval_hess always leaves 0 (structural zeros): on the workspace path a launch
+// stores them in its first W pass only (round 6); the on-chip record (WPack) has no slot for them.  2-link arm
+// (two_link_fast.h eval_hess: q_A enters only through gravity, the torques linearly): row 0 is zero in columns 2..5,
+// rows 2 and 3 in columns 0, 4 and 5.
 template <class Model>
-__device__ constexpr bool w_struct_zero(int, int) { return false; }
+__host__ __device__ constexpr bool w_struct_zero(int, int) { return false; }
 template <>
-__device__ constexpr bool w_struct_zero<TwoLinkArm>(int r, int j) { return (r == 0 && j >= 2) || (r >= 2 && (j == 0 || j >= 4)); }
+__host__ __device__ constexpr bool w_struct_zero<TwoLinkArm>(int r, int j) { return (r == 0 && j >= 2) || (r >= 2 && (j == 0 || j >= 4)); }
+// Packed record of the x rows of W_k for the on-chip W path of the unbounded exact-Hessian kernel (sqp_group_kernel,
+// WLDS): PK doubles per stage, idx(r, j) = slot of W_k[r][j] (x row r, column j of (x, u)), -1 for a structural zero.
+// PK = 0: the model has no packing and keeps the workspace path.  2-link arm: eval_hess writes W[i][j] and W[j][i]
+// from one variable, so the 14 non-zero entries of the x rows are 10 distinct values:
+//   slot  0     1     2     3     4     5     6     7     8     9
+//   W     [0][0] [0][1] [1][1] [1][2] [1][3] [1][4] [1][5] [2][2] [2][3] [3][3]
+template <class Model>
+struct WPack {
+    static constexpr int PK = 0;
+    __host__ __device__ static constexpr int idx(int, int) { return -1; }
+};
+template <>
+struct WPack<TwoLinkArm> {
+    static constexpr int PK = 10;
+    __host__ __device__ static constexpr int idx(int r, int j) {
+        if (w_struct_zero<TwoLinkArm>(r, j)) return -1;
+        const int a = r < j ? r : j, b = r < j ? j : r;   // (a, b), a <= b: the entry eval_hess computes
+        return a == 0 ? b : (a == 1 ? 1 + b : (a == 2 ? 5 + b : 9));
+    }
+};
+// first column whose structural zeros sit in the same x rows as column j's (j itself when there is none before it)
+template <class Model>
+__host__ __device__ constexpr int wpack_col_rep(int j) {
+    for (int q = 0; q < j; ++q) {
+        bool same = true;
+        for (int r = 0; r < Model::NX; ++r) same = same && ((WPack<Model>::idx(r, q) < 0) == (WPack<Model>::idx(r, j) < 0));
+        if (same) return q;
+    }
+    return j;
+}
 constexpr int kGroupLanes = 16;
 constexpr int kGroupsPerWave = 4;
 
@@ -84,10 +104,17 @@ __host__ __device__ constexpr int group_hess_doubles(int nx, int nu) { return nx
 // the host reserves the bounded size, the largest.
 // xb (the interior-point variant, never with `bounded`): the per-stage z_l, z_u, Sigma, b, z_u - z_l of
 // (x_{k+1} | u_k) after the W blocks, in place of the bounded solves' rows.
-__host__ __device__ constexpr int group_ws_doubles(int nx, int nu, int N, bool bounded = true, bool xb = false) {
-    return N * nu * (nx + nu + 1) + N * group_hess_doubles(nx, nu) + (bounded ? N * nu * (nx + 2 * nu + 1) : 0) +
-           (xb ? 5 * N * (nx + nu) : 0);
+// w_onchip (the unbounded exact-Hessian kernel of a model with a packed W record, WPack): the W blocks stay in LDS, so
+// the kernel strides instances by K | kff alone (420 doubles at cfg#2).
+__host__ __device__ constexpr int group_ws_doubles(int nx, int nu, int N, bool bounded = true, bool xb = false,
+                                                  bool w_onchip = false) {
+    return N * nu * (nx + nu + 1) + (w_onchip ? 0 : N * group_hess_doubles(nx, nu)) +
+           (bounded ? N * nu * (nx + 2 * nu + 1) : 0) + (xb ? 5 * N * (nx + nu) : 0);
 }
+// the cfg#2 shape (2-link arm, N = 30, unbounded): four instances per workgroup within 40,960 B of LDS, so that four
+// workgroups (one per SIMD) fit a CU -- the on-chip W record lives in arrays that are dead while it is alive and adds
+// nothing to this
+static_assert(kGroupsPerWave * group_lds_doubles(4, 2, 2, 30, false, false, false) * 8 <= 40960, "cfg#2 LDS budget");
 
 struct GroupWork {
     double* ws;
@@ -216,10 +243,13 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
 
     // ---- LDS views of this instance ----
     double* const sX = shm + gi * group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB);  // [N+1][NX]
-    double* const sDX = sX + (N + 1) * NX;                         // [N+1][NX]
-    double* const sD = sDX + (N + 1) * NX;                         // [N+1][NX]
-    double* const sU = sD + (N + 1) * NX;                          // [N][NU]
-    double* const sDU = sU + N * NU;                               // [N][NU]
+    // sD | sDX | sDU are contiguous: between the W pass and the step sweep of an iteration all three are dead (d / lam
+    // in sD: the W pass is its last reader; sDX, sDU: the previous step, consumed by the update) and, on the on-chip W
+    // path (WLDS), sD + NX .. holds the packed W records (sW) -- d_0 = 0 in sD[0..NX) stays
+    double* const sU = sX + (N + 1) * NX;                          // [N][NU]
+    double* const sD = sU + N * NU;                                // [N+1][NX]
+    double* const sDX = sD + (N + 1) * NX;                         // [N+1][NX]
+    double* const sDU = sDX + (N + 1) * NX;                        // [N][NU]
     double* const sF = sDU + N * NU;                               // [N][NX]
     double* const sC = sF + N * NX;                                // [N][NX]
     double* const sFq = sC + N * NX;                               // [N][NA*NQ]   h da/dq
@@ -229,9 +259,16 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     double* const sHold = sR + N * NX;                             // [N][NU]      bound a control is held at
     double* const sLin = sHold + (BOUNDED ? N * NU : 0);           // linear mode: Fq | Fqd | Fu | xdot
     constexpr int NY = NX + NU;
-    double* const wK = gw.ws + slot * (int64_t)group_ws_doubles(NX, NU, N, BOUNDED, XB);  // [N][NU][NS+1]
+    // On-chip W path: the unbounded exact-Hessian solve of a control-affine model with a packed W record that fits the
+    // dead arrays (PK <= 2 NX + NU per stage; PK >= NX for the W pass's write order, below).  It solves the QP once per
+    // iteration, with no step sweep between the W pass and the Riccati sweep; the control-bounded and interior-point
+    // variants solve it again after step sweeps that rewrite sDX, sD and sDU, and keep W in the workspace.
+    constexpr int PK = WPack<Model>::PK;
+    constexpr bool WLDS = EXACT && !BOUNDED && !XB && IsControlAffine<Model>::value && PK >= NX && PK <= 2 * NX + NU;
+    double* const wK = gw.ws + slot * (int64_t)group_ws_doubles(NX, NU, N, BOUNDED, XB, WLDS);  // [N][NU][NS+1]
     constexpr int KZ = NX + NU, HW = group_hess_doubles(NX, NU);
     double* const wH = wK + N * NU * (NS + 1);  // EXACT: [N][HW] = W_k x rows [NX][KZ] | W_k uu block [NU][NU]
+    double* const sW = sD + NX;                 // WLDS: [N][PK] packed W_k x rows, over sD[1..], sDX and sDU
     constexpr int NR = NS + NU + 1;             // BOUNDED: [N][NU][NR] = un-held [H_wx | -R | H_ww | h_w] rows
     double* const wRel = wH + N * HW;
     bool w_zeros_stored = false;   // W_k's structural zeros are in the workspace (this launch's first W pass stored them)
@@ -279,6 +316,23 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // x-lane factor for the sweeps' per-stage masking: one FP64 multiply where a 64-bit select is two cndmasks (the
     // masked values are finite sums of this instance's own data, so 0 * v == 0)
     const double lxf = lx ? 1.0 : 0.0;
+    // WLDS: slot of W_k[r][j] in the packed record and its blend factor.  A structural zero, and every column of a
+    // lane without an x row, reads slot 0 (finite) under a factor 0 -- the factor takes the place of the x-lane factor
+    // at the uses of W, so the sweep gains no select; columns with the same zero pattern share one factor.
+    int wofs[KZ];
+    double wm[KZ];
+#pragma unroll
+    for (int j = 0; j < KZ; ++j) {
+        wofs[j] = 0;
+        bool nz = false;
+#pragma unroll
+        for (int r2 = 0; r2 < NX; ++r2)
+            if (lx && r == r2 && WPack<Model>::idx(r2, j) >= 0) {
+                wofs[j] = WPack<Model>::idx(r2, j);
+                nz = true;
+            }
+        wm[j] = wpack_col_rep<Model>(j) < j ? wm[wpack_col_rep<Model>(j)] : (nz ? 1.0 : 0.0);
+    }
     const int rq = r < NQ ? r : 0;                    // q column of a q-lane (clamped)
     const double Rr = lu ? w[NX + ru] : 0.0;          // R of this lane's u row
     double dgx[NS];                                    // XB: this x-lane's diagonal entry of P~ (barrier Sigma)
@@ -1033,7 +1087,10 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             }
             double Prow[NS], pvr;
             const double lxm = lx ? 1.0 : 0.0;
-            // W_k row rx and uu block from the workspace, loaded one stage ahead into one buffer.  (Round 2 used two
+            // W_k row rx and uu block, loaded one stage ahead into one buffer: from the workspace, or (WLDS) row rx of
+            // the packed record in LDS through this lane's slots wofs, a structural zero reading slot 0 under wm = 0;
+            // the records were written by the other lanes of this wave, and LDS serves a wave's accesses in order.
+            // (Round 2 used two
             // buffers two stages ahead; once the control-affine sweep dropped the uu block, the second buffer's
             // registers cost more than the load latency it hid: 0.1875 -> 0.1808 ms with one buffer)
             struct Wb {
@@ -1042,7 +1099,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             Wb w0;
             auto load_w = [&](int k, Wb& b) {
 #pragma unroll
-                for (int j = 0; j < KZ; ++j) b.r[j] = wH[k * HW + rx * KZ + j];   // row rx; masked at its uses
+                for (int j = 0; j < KZ; ++j)   // row rx; masked at its uses
+                    b.r[j] = WLDS ? sW[k * PK + wofs[j]] : wH[k * HW + rx * KZ + j];
                 if constexpr (!CAFF) {
 #pragma unroll
                     for (int j = 0; j < NU * NU; ++j) b.u[j] = wH[k * HW + NX * KZ + j];
@@ -1159,7 +1217,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
 #pragma unroll
                     for (int q = 0; q < NX; ++q) tb[q] = Tb[q][a];
                     Ycol[a] = colA(T[a], acol, tb) - rdg[a];
-                    if constexpr (EXACT) Ycol[a] = fma(lxm, wr[NX + a], Ycol[a]);   // H_wx[a][r] += W_ux[a][r] (x-lanes)
+                    // H_wx[a][r] += W_ux[a][r] (x-lanes; WLDS: the x-lanes whose entry is not a structural zero)
+                    if constexpr (EXACT) Ycol[a] = fma(WLDS ? wm[NX + a] : lxm, wr[NX + a], Ycol[a]);
                 }
                 // BOUNDED: the un-held stage rows [H_wx | -R | H_ww | h_w] (lane j < NS: column j; lanes NS.. the H_ww
                 // columns and h_w, the idle lanes duplicating h_w) -- the step sweep forms the multiplier of a held
@@ -1333,7 +1392,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 {
                     const int col = r < NS ? r : NS;
 #pragma unroll
-                    for (int a = 0; a < NU; ++a) ws_store(&wK[(k * NU + a) * (NS + 1) + col], -(r < NS ? Kcol[a] : kff[a]));
+                    for (int a = 0; a < NU; ++a) wK[(k * NU + a) * (NS + 1) + col] = -(r < NS ? Kcol[a] : kff[a]);
                 }
                 if constexpr (LAST) return;
                 // A^T P_xx A (row r) from the broadcast P_xx, p~_x = A^T mv + Q (x_k - r_{k-1})
@@ -1395,7 +1454,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 for (int j = 0; j < NS; ++j) {
                     double v = j < NX ? Pn[j] + qoh[j] : rdg[j - NX];
                     if constexpr (EXACT) {
-                        if (j < NX) v = fma(lxm, wr[j], v);   // W_xx row r (x-lanes; the mask folded into the add)
+                        if (j < NX) v = fma(WLDS ? wm[j] : lxm, wr[j], v);   // W_xx row r (x-lanes; the mask folded into the add)
                     }
 #pragma unroll
                     for (int a = 0; a < NU; ++a) v = fma(-Ycol[a], j < NX ? Kb[a][j] : Ku[a][j - NX], v);
@@ -1510,7 +1569,12 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         if constexpr (EXACT) {
             // stage-parallel: W_k = h sum_s lam_{k+1,NQ+s} d^2 acc_s/d(x_k,u_k)^2 (lam from the adjoint, in sD)
             __builtin_amdgcn_wave_barrier();
-            for (int k = gl; k < N; k += G) {
+            // W_k of stage k on lane k mod 16.  WLDS: the packed record goes to sW[k], over sD[1..] | sDX | sDU.  Record k
+            // starts at double NX + PK k of sD and lam_{k'+1} ends at NX (k' + 2), so with PK >= NX writing record k can
+            // only overwrite the lam operands of stages k' >= k.  The stages are therefore taken in rounds of 16 from the
+            // last round down, for every N: the stages above a round are done, and within a round every lane's lam loads
+            // precede every lane's stores in program order (one wave; LDS serves its accesses in order).
+            auto w_stage = [&](int k) {
                 double x[NX], u[NU], la[NA], W[KZ * KZ];
 #pragma unroll
                 for (int r2 = 0; r2 < NX; ++r2) x[r2] = sX[k * NX + r2];
@@ -1518,29 +1582,47 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 for (int c = 0; c < NU; ++c) u[c] = sU[k * NU + c];
 #pragma unroll
                 for (int s2 = 0; s2 < NA; ++s2) la[s2] = h * sD[(k + 1) * NX + NQ + s2];
+                if constexpr (WLDS) __builtin_amdgcn_wave_barrier();   // (compiler: no store of this round above a load)
                 Model::eval_hess(x, u, la, W);
-                double* const dst = wH + k * HW;
+                if constexpr (WLDS) {
+                    static_assert(!WLDS || PK >= NX, "write order of the W pass");
 #pragma unroll
-                for (int r2 = 0; r2 < NX; ++r2)
+                    for (int r2 = 0; r2 < NX; ++r2)
 #pragma unroll
-                    for (int j = 0; j < KZ; ++j)
-                        if (!(MMPC_GROUP_WZERO_ONCE && w_struct_zero<Model>(r2, j)) || !w_zeros_stored)
-                            ws_store(&dst[r2 * KZ + j], W[r2 * KZ + j]);
-                if constexpr (!CAFF) {
+                        for (int j = r2; j < KZ; ++j)
+                            if (WPack<Model>::idx(r2, j) >= 0) sW[k * PK + WPack<Model>::idx(r2, j)] = W[r2 * KZ + j];
+                } else {
+                    double* const dst = wH + k * HW;
 #pragma unroll
-                    for (int a = 0; a < NU; ++a)
+                    for (int r2 = 0; r2 < NX; ++r2)
 #pragma unroll
-                        for (int b = 0; b < NU; ++b) ws_store(&dst[NX * KZ + a * NU + b], W[(NX + a) * KZ + NX + b]);
+                        for (int j = 0; j < KZ; ++j)
+                            if (!w_struct_zero<Model>(r2, j) || !w_zeros_stored) dst[r2 * KZ + j] = W[r2 * KZ + j];
+                    if constexpr (!CAFF) {
+#pragma unroll
+                        for (int a = 0; a < NU; ++a)
+#pragma unroll
+                            for (int b = 0; b < NU; ++b) dst[NX * KZ + a * NU + b] = W[(NX + a) * KZ + NX + b];
+                    }
                 }
-            }
-            w_zeros_stored = true;
-            MMPC_PHASE(9);   // (timing build: "check" = the stop test and this W pass up to its fence)
-            // the stores of the other lanes of this wave must be visible to the sweep's loads
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            };
+            if constexpr (WLDS) {
+                for (int k0 = ((N - 1) / G) * G; k0 >= 0; k0 -= G)
+                    if (k0 + gl < N) w_stage(k0 + gl);
+                MMPC_PHASE(9);   // (timing build: "check" = the stop test and this W pass)
+                // the records of the other lanes of this wave are in LDS before the sweep's loads: program order
+                __builtin_amdgcn_wave_barrier();
+            } else {
+                for (int k = gl; k < N; k += G) w_stage(k);
+                w_zeros_stored = true;
+                MMPC_PHASE(9);   // (timing build: "check" = the stop test and this W pass up to its fence)
+                // the stores of the other lanes of this wave must be visible to the sweep's loads
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #ifdef MMPC_PHASE_FENCE_IN_LOAD
-            MMPC_PHASE(0);   // (diagnostic: the fence's wait for the W stores, accumulated with the load phase)
+                MMPC_PHASE(0);   // (diagnostic: the fence's wait for the W stores, accumulated with the load phase)
 #endif
+            }
         }
         // exact Hessian in this iteration's QP solves (false after a Gauss-Newton fallback)
         bool use_w = EXACT;
