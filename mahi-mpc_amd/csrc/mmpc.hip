@@ -655,15 +655,7 @@ int set_dynamic_lds(K kernel, size_t bytes) {
     return MMPC_OK;
 }
 
-// the KKT solver a solve of B instances runs (opts.kkt_solver, or the AUTO choice)
-int resolve_kkt_solver_base(const mmpc_handle* h, int64_t B);
-int resolve_kkt_solver(const mmpc_handle* h, int64_t B) {
-    const int s = resolve_kkt_solver_base(h, B);
-    // state bounds (interior-point variant): the Riccati solvers only; the group kernel when its LDS layout fits
-    if (h->x_bounded && h->opts.kkt_solver == MMPC_KKT_AUTO && s == MMPC_KKT_CONDENSED)
-        return group_lds_bytes(h->info, h->nq, true, true) <= kMaxGroupLds ? MMPC_KKT_RICCATI_GROUP : MMPC_KKT_RICCATI;
-    return s;
-}
+// opts.kkt_solver, or the AUTO choice before state bounds are considered
 int resolve_kkt_solver_base(const mmpc_handle* h, int64_t B) {
     const mmpc_model_info& mi = h->info;
     if (h->opts.kkt_solver != MMPC_KKT_AUTO) return h->opts.kkt_solver;
@@ -689,6 +681,14 @@ int resolve_kkt_solver_base(const mmpc_handle* h, int64_t B) {
     }
     if (glds <= kMaxGroupLds / 2 && B <= 4096) return MMPC_KKT_RICCATI_GROUP;
     return MMPC_KKT_RICCATI;
+}
+// the KKT solver a solve of B instances runs
+int resolve_kkt_solver(const mmpc_handle* h, int64_t B) {
+    const int s = resolve_kkt_solver_base(h, B);
+    // state bounds (interior-point variant): the Riccati solvers only; the group kernel when its LDS layout fits
+    if (h->x_bounded && h->opts.kkt_solver == MMPC_KKT_AUTO && s == MMPC_KKT_CONDENSED)
+        return group_lds_bytes(h->info, h->nq, true, true) <= kMaxGroupLds ? MMPC_KKT_RICCATI_GROUP : MMPC_KKT_RICCATI;
+    return s;
 }
 
 // Exact-Hessian support of a model / solve (mmpc_opts.hessian): second derivatives, the lane-distributed path
@@ -745,10 +745,30 @@ int launch_group(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const So
     sqp_group_kernel<Model, BOUNDED, XB, EXACT><<<grid, block, lds, stream>>>(p, gwk);
     return MMPC_OK;
 }
+// the 16-lane kernel of model M for (ub: control bounds only, xb: state bounds, exact Hessian); `what` names the launch
+// in an error text.  The built-in 2-link arm's kernels live in the units of group_launch.h.
+template <class M>
+int dispatch_group(bool ub, bool xb, bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                   const SolveParams& p, GroupWork gwk, const char* what) {
+    if constexpr (std::is_same<M, TwoLinkArm>::value) {
+        const hipError_t e = (ub || xb) ? launch_group_two_link_bounded(xb, exact, grid, block, lds, stream, p, gwk)
+                                        : launch_group_two_link(exact, grid, block, lds, stream, p, gwk);
+        return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    } else {
+        if constexpr (exact_capable<M>()) {
+            if (exact)
+                return xb   ? launch_group<M, false, true, true>(grid, block, lds, stream, p, gwk)
+                       : ub ? launch_group<M, true, false, true>(grid, block, lds, stream, p, gwk)
+                            : launch_group<M, false, false, true>(grid, block, lds, stream, p, gwk);
+        }
+        return xb   ? launch_group<M, false, true>(grid, block, lds, stream, p, gwk)
+               : ub ? launch_group<M, true>(grid, block, lds, stream, p, gwk)
+                    : launch_group<M, false>(grid, block, lds, stream, p, gwk);
+    }
+}
 
 // Riccati workspace (sqp_lane.h / sqp_group.h layouts), grown on demand.  Growth is synchronous:
 // hipFree waits for the kernels still using the old buffer.
-constexpr size_t kExitCountBytes = 256;
 int ensure_workspace_bytes(mmpc_handle* h, size_t bytes, double** out) {
     int dev = -1;
     MMPC_HIP(hipGetDevice(&dev));
@@ -758,9 +778,7 @@ int ensure_workspace_bytes(mmpc_handle* h, size_t bytes, double** out) {
         if (h->ws) MMPC_HIP(hipFree(h->ws));
         h->ws = nullptr;
         h->ws_bytes = 0;
-        // + the 16-lane kernel's finish counter (SolveParams::exit_count), zeroed once here and reset by every launch
-        MMPC_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), bytes + kExitCountBytes));
-        MMPC_HIP(hipMemset(reinterpret_cast<char*>(h->ws) + bytes, 0, kExitCountBytes));
+        MMPC_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), bytes));
         h->ws_bytes = bytes;
         h->ws_dev = dev;
     }
@@ -891,7 +909,6 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     p.tail_lws_block = 0;
     p.tail_lws_ss = p.tail_lws_zl = 0;
     p.gpw = kGroupsPerWave;
-    p.exit_count = nullptr;
     // any bound pointer selects the kernels' BOUNDED variant (projected GN-SQP, sqp_wave.h); host entry
     // points pass NULL for bounds that are all infinite
     const bool bounded = u_lb || u_ub;
@@ -924,35 +941,10 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
         dim3 grid(grid1d(B, kGroupsPerWave)), block(64);
         const int hess = resolve_hessian(h, solver, bounded);
         if (hess < 0) return hess;
-        SolveParams pg = p;
-#if MMPC_GROUP_EXIT_HOLD
-        // resident finish: when the whole grid is resident at once (one wave per SIMD by registers, the
-        // workgroups per CU the LDS allows), finished waves stay resident until the launch's last waves have finished
-        if ((rc = query_cu_count(h))) return rc;
-        const int64_t resident = static_cast<int64_t>(h->cu_count) * std::min<int64_t>(4, (160 * 1024) / std::max<size_t>(lds, 1));
-        if (grid.x >= 2 && static_cast<int64_t>(grid.x) <= resident)
-            pg.exit_count = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(lw.ws) + h->ws_bytes);
-#endif
         rc = with_model(mi.model_id, [&](auto* m) {
             using M = std::remove_pointer_t<decltype(m)>;
-            if constexpr (std::is_same<M, TwoLinkArm>::value) {   // the units of group_launch.h
-                const bool exact = hess == MMPC_HESSIAN_EXACT;
-                const hipError_t e =
-                    (bounded || xb) ? launch_group_two_link_bounded(xb, exact, grid, block, lds, stream, pg, gwk)
-                                    : launch_group_two_link(exact, grid, block, lds, stream, pg, gwk);
-                return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string("group kernel launch: ") +
-                                                                          hipGetErrorString(e));
-            } else {
-                if constexpr (exact_capable<M>()) {
-                    if (hess == MMPC_HESSIAN_EXACT)
-                        return xb        ? launch_group<M, false, true, true>(grid, block, lds, stream, pg, gwk)
-                               : bounded ? launch_group<M, true, false, true>(grid, block, lds, stream, pg, gwk)
-                                         : launch_group<M, false, false, true>(grid, block, lds, stream, pg, gwk);
-                }
-                if (xb) return launch_group<M, false, true>(grid, block, lds, stream, pg, gwk);
-                return bounded ? launch_group<M, true>(grid, block, lds, stream, pg, gwk)
-                               : launch_group<M, false>(grid, block, lds, stream, pg, gwk);
-            }
+            return dispatch_group<M>(bounded && !xb, xb, hess == MMPC_HESSIAN_EXACT, grid, block, lds, stream, p, gwk,
+                                     "group kernel launch");
         });
         if (rc) return rc;
         MMPC_HIP(hipGetLastError());
@@ -1028,27 +1020,8 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
             rc = with_model(mi.model_id, [&](auto* m) {
                 using M = std::remove_pointer_t<decltype(m)>;
                 if constexpr (M::NX + M::NU < kGroupLanes) {
-                    if constexpr (std::is_same<M, TwoLinkArm>::value) {
-                        const bool ex = hess == MMPC_HESSIAN_EXACT;
-                        const hipError_t e =
-                            (xb || ub) ? launch_group_two_link_bounded(xb, ex, rgrid, rblock, tp.lds, stream, pr, gwk)
-                                       : launch_group_two_link(ex, rgrid, rblock, tp.lds, stream, pr, gwk);
-                        return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string("resume launch: ") +
-                                                                                  hipGetErrorString(e));
-                    } else {
-                        if constexpr (exact_capable<M>()) {
-                            if (xb && hess == MMPC_HESSIAN_EXACT)
-                                return launch_group<M, false, true, true>(rgrid, rblock, tp.lds, stream, pr, gwk);
-                        }
-                        if (xb) return launch_group<M, false, true>(rgrid, rblock, tp.lds, stream, pr, gwk);
-                        if constexpr (exact_capable<M>()) {
-                            if (hess == MMPC_HESSIAN_EXACT)
-                                return ub ? launch_group<M, true, false, true>(rgrid, rblock, tp.lds, stream, pr, gwk)
-                                          : launch_group<M, false, false, true>(rgrid, rblock, tp.lds, stream, pr, gwk);
-                        }
-                        return ub ? launch_group<M, true>(rgrid, rblock, tp.lds, stream, pr, gwk)
-                                  : launch_group<M, false>(rgrid, rblock, tp.lds, stream, pr, gwk);
-                    }
+                    return dispatch_group<M>(ub, xb, hess == MMPC_HESSIAN_EXACT, rgrid, rblock, tp.lds, stream, pr, gwk,
+                                             "resume launch");
                 } else {
                     return fail(MMPC_ERR_UNSUPPORTED, "tail hand-over: nx + nu >= 16");   // tail_plan excludes it
                 }
@@ -1889,9 +1862,11 @@ const char* mmpc_last_error(void) { return g_last_error.c_str(); }
 static void merge_phase_tables(unsigned long long* out, const unsigned long long* t, int n) {
     for (int i = 0; i < n; ++i) out[i] = (i >= 10 && i <= 12) ? std::max(out[i], t[i]) : out[i] + t[i];
 }
-// the first n (<= kPhaseSlots) slots of the merged tables of every translation unit
+// the first n slots of the merged tables of every translation unit (kPhaseTableSlots: kPhaseSlots in the timing build,
+// 16 otherwise)
 int mmpc_debug_phase_table(unsigned long long* out, int n, int reset) {
-    if (!out || n < 16 || n > kPhaseSlots) return fail(MMPC_ERR_INVALID_ARG, "null or n out of 16 .. kPhaseSlots");
+    if (!out || n < 16 || n > kPhaseTableSlots)
+        return fail(MMPC_ERR_INVALID_ARG, "null or n out of 16 .. the table's size (16 outside the timing build)");
     MMPC_HIP(phase_table_read(out, n, reset != 0));   // this unit's table
     std::vector<unsigned long long> t(static_cast<size_t>(n));
     MMPC_HIP(lane_phase_cycles(t.data(), n, reset != 0));   // the lane kernels' unit (lane_launch.h)

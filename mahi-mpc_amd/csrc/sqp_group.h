@@ -24,18 +24,6 @@
 
 namespace mmpc {
 
-#ifndef MMPC_GROUP_BOUNDED_PAIRS
-#define MMPC_GROUP_BOUNDED_PAIRS 0
-#endif
-#ifndef MMPC_GROUP_XB_PAIRS
-#define MMPC_GROUP_XB_PAIRS 1
-#endif
-#ifndef MMPC_GROUP_EXIT_HOLD   // resident finish of the 16-lane kernel; 0: waves exit as they finish
-#define MMPC_GROUP_EXIT_HOLD 0
-#endif
-#ifndef MMPC_GROUP_WB_COALESCED   // A/B switch: V written back 16 consecutive doubles per store instruction
-#define MMPC_GROUP_WB_COALESCED 0
-#endif
 // Entries of W_k's x rows that Model::eval_hess always leaves 0 (structural zeros): on the workspace path a launch
 // stores them in its first W pass only (round 6); the on-chip record (WPack) has no slot for them.  2-link arm
 // (two_link_fast.h eval_hess: q_A enters only through gravity, the torques linearly): row 0 is zero in columns 2..5,
@@ -218,12 +206,6 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     const int gi = threadIdx.x / G;
     [[maybe_unused]] const int lane0 = threadIdx.x;
     MMPC_PHASE_DECL
-#ifdef MMPC_GROUP_SLEEP_EXIT
-    const unsigned long long sl_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#if MMPC_GROUP_EXIT_HOLD
-    const unsigned long long fin_t0 = __builtin_amdgcn_s_memrealtime();   // resident finish: this wave's start
-#endif
     const int gbase = gi * G;  // first lane of this instance's group
     // slot of this group in the launch: the instance itself, or (resume launch, p.tail_idx) an entry of the lane
     // kernel's hand-over list
@@ -1470,7 +1452,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             // the control-bounded sweep one stage per trip (its hold logic and relaxation rows fill the registers: two
             // stages in flight spilled to scratch inside the loop)
             using F_ = std::false_type;
-            if constexpr ((BOUNDED && !MMPC_GROUP_BOUNDED_PAIRS) || (XB && (EXACT || !MMPC_GROUP_XB_PAIRS))) {
+            if constexpr (BOUNDED || (XB && EXACT)) {
                 for (int k = N - 1; k >= 1; --k) stage(k, F_{}, w0);
                 stage(0, std::true_type{}, w0);
             } else if ((N - 1) & 1) {
@@ -1619,9 +1601,6 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 // the stores of the other lanes of this wave must be visible to the sweep's loads
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#ifdef MMPC_PHASE_FENCE_IN_LOAD
-                MMPC_PHASE(0);   // (diagnostic: the fence's wait for the W stores, accumulated with the load phase)
-#endif
             }
         }
         // exact Hessian in this iteration's QP solves (false after a Gauss-Newton fallback)
@@ -1972,14 +1951,6 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     if (!valid) return;
     // ---- write back V (reference layout), stage-parallel ----
     double* Vout = p.V + inst * (int64_t)NV;
-#if MMPC_GROUP_WB_COALESCED
-    // V element e on lane e mod 16: each store instruction writes 16 consecutive doubles of the instance's row
-    for (int e = gl; e < NV; e += G) {
-        const int k = e / ND, r = e - k * ND;
-        Vout[e] = r < NX ? sX[k * NX + r] : sU[k * NU + r - NX];
-    }
-    if (false)
-#endif
     for (int k = gl; k <= N; k += G) {
 #pragma unroll
         for (int r = 0; r < NX; ++r) Vout[k * ND + r] = sX[k * NX + r];
@@ -1996,48 +1967,6 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     }
     MMPC_PHASE(7);
     MMPC_PHASE_FLUSH
-#ifdef MMPC_GROUP_SLEEP_EXIT
-    // diagnostic A/B (lib_var builds only): a finished wave sleeps MMPC_GROUP_SLEEP_EXIT % of its own duration before
-    // it exits (s_memrealtime, no memory traffic), so the chip stays occupied while the waves of the last iteration run
-    {
-        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        const unsigned long long until = t1 + (t1 - sl_t0) * MMPC_GROUP_SLEEP_EXIT / 100;
-#ifdef MMPC_GROUP_SPIN_EXIT   // ... busy with FP64 FMAs instead of sleeping (the power draw of a running wave)
-        double sp = (double)threadIdx.x;
-        while (__builtin_amdgcn_s_memrealtime() < until) {
-            for (int i = 0; i < 64; ++i) sp = fma(sp, 0.999, 1e-3);
-            asm volatile("" : "+v"(sp));
-        }
-#else
-        while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(32);
-#endif
-    }
-#endif
-#if MMPC_GROUP_EXIT_HOLD
-    // resident finish: a wave that finishes while other waves of the launch still run stays resident,
-    // sleeping, until at most 1/32 of the launch's waves are still running (or, a bound, half its own duration has
-    // passed).  Waves that ran on a chip whose other waves had left ran their last iteration up to ~1.5x slower
-    // (cfg#2 at tol 1e-5, profiles/r06/sleep).  One atomic per wave; the wave that finishes last resets the counter
-    // for the next launch; polls every ~2 us (s_sleep, no traffic in between).
-    if (!resume && p.exit_count) {
-        int done_before = 0;
-        if (threadIdx.x == 0) done_before = atomicAdd(p.exit_count, 1);
-        done_before = __builtin_amdgcn_readfirstlane(done_before);   // lane 0 (group 0 of a wave is always valid)
-        const int waves = (int)gridDim.x;
-        if (done_before + 1 >= waves) {
-            if (threadIdx.x == 0) __hip_atomic_store(p.exit_count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-            const unsigned long long until = t1 + (t1 - fin_t0) / 2;
-            const int leave = waves - max(1, waves / 32);   // finished count at which the waiting waves leave
-            while (__builtin_amdgcn_s_memrealtime() < until) {
-                __builtin_amdgcn_s_sleep(64);
-                const int n = __hip_atomic_load(p.exit_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (n == 0 || n >= leave) break;   // 0: the last wave has reset it
-            }
-        }
-    }
-#endif
 }
 
 }  // namespace mmpc

@@ -25,50 +25,6 @@
 #include "models.h"
 #include "sqp_wave.h"
 
-// A/B switches of the fp32-factor instantiations (diagnostic builds only; defaults are the shipped choice)
-#ifndef MMPC_LANE_YLO32
-#define MMPC_LANE_YLO32 1
-#endif
-#ifndef MMPC_LANE_JACH32
-#define MMPC_LANE_JACH32 1
-#endif
-#ifndef MMPC_LANE_LB32
-#define MMPC_LANE_LB32 1
-#endif
-#ifndef MMPC_LANE_XB_BATCHED
-#define MMPC_LANE_XB_BATCHED 1
-#endif
-#ifndef MMPC_LANE_FWD32
-#define MMPC_LANE_FWD32 1
-#endif
-#ifndef MMPC_LANE_WPE32
-#define MMPC_LANE_WPE32 1
-#endif
-#ifndef MMPC_LANE_C_RECOMPUTE   // step sweep: c_k from its own model evaluation instead of the stored C (round 6)
-#define MMPC_LANE_C_RECOMPUTE 1
-#endif
-#ifndef MMPC_LANE_C_NOSTORE   // no C record: the backward sweep recomputes c_k too (requires MMPC_LANE_C_RECOMPUTE)
-#define MMPC_LANE_C_NOSTORE 1
-#endif
-#ifndef MMPC_LANE_LAZY_DXU   // unbounded solves: DX / DU stored in the first iteration only (regenerated on demand)
-#define MMPC_LANE_LAZY_DXU 1
-#endif
-#ifndef MMPC_LANE_KPACK   // gain record with H_ww^-1 instead of K_u (kgain_idx; not for control-bounded solves)
-#define MMPC_LANE_KPACK 1
-#endif
-#ifndef MMPC_LANE_LS_HANDOVER   // a rejected full step after the first iteration is handed to the resume launch
-#define MMPC_LANE_LS_HANDOVER 1
-#endif
-#ifndef MMPC_LANE_XTRA_K
-#define MMPC_LANE_XTRA_K 0
-#endif
-#ifndef MMPC_LANE_XB_EARLY
-#define MMPC_LANE_XB_EARLY 1
-#endif
-#ifndef MMPC_LANE_XB_EARLY_STEP
-#define MMPC_LANE_XB_EARLY_STEP MMPC_LANE_XB_EARLY
-#endif
-
 namespace mmpc {
 
 // Workspace layout, stage-major: [64-instance block][stage k = 0..N+1][field][lane].  All fields of
@@ -104,7 +60,7 @@ struct StageFields {
     static constexpr int X = 0;             // x_k
     static constexpr int U = X + NX;        // u_k
     static constexpr int R = U + NU;        // r_k (target of F(x_k, u_k))
-    static constexpr int C = R + NX;        // defect c_k = F_k - x_{k+1}
+    static constexpr int C = R + NX;        // (unused slot: the sweeps recompute the defect c_k = F_k - x_{k+1})
     static constexpr int D = C + NX;        // d_k (defect propagation)
     static constexpr int DX = D + NX;       // dx_k
     static constexpr int DU = DX + NX;      // du_k
@@ -233,12 +189,9 @@ __device__ __forceinline__ gmem<double>* stage_ptr(double* wsb, int64_t k, int S
 template <class Model, class FT = double, bool BOUNDED = false, bool XB = false, bool EXACT = false>
 // one wave per SIMD by design (P~ in LDS, ~40 KB per wave): telling the scheduler so lets it schedule for latency
 // rather than for a second wave's registers (cfg#3: 12.06 -> 11.94 ms).  The fp32-factor variant's P~ takes 20 KB, so
-// 8 waves fit a CU's LDS: MMPC_LANE_WPE32 = 2 (A/B builds) asks for 2 waves per SIMD there (256 registers)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(std::is_same<FT, float>::value ? MMPC_LANE_WPE32 : 1,
-                                                                    std::is_same<FT, float>::value ? MMPC_LANE_WPE32
-                                                                                                   : 1))) void
-sqp_lane_kernel(SolveParams p,
-                                                                                                 LaneWork lw) {
+// 8 waves would fit a CU's LDS, but it too runs one wave per SIMD: two (256 registers each) measured slower
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
+sqp_lane_kernel(SolveParams p, LaneWork lw) {
     static_assert(!(BOUNDED && XB), "the interior-point variant handles the control bounds itself");
     static_assert(!EXACT || (HasHess<Model>::value && std::is_same<FT, double>::value),
                   "exact Hessian: fp64 solves of models with second derivatives");
@@ -270,10 +223,10 @@ sqp_lane_kernel(SolveParams p,
     // the other, which the step sweep fills with the full-step point (x_k + dx_k, u_k + du_k) -- an accepted full step
     // (99.7 % of the cfg#3 iterations) swaps the names instead of running the update pass over the workspace
     constexpr bool SWAP = !BOUNDED && !XB;
-    constexpr bool KPACK = !BOUNDED && MMPC_LANE_KPACK;   // gain record layout (kgain_idx)
+    constexpr bool KPACK = !BOUNDED;   // gain record layout (kgain_idx)
     // lazy step records (DX / DU, below): unbounded solves; not with the exact Hessian, whose kernel ran 11.19 -> 11.74 ms
     // with them (cfg#3 exact, the regeneration's registers: profiles/r06/kpack/abx)
-    constexpr bool LAZY = SWAP && !EXACT && MMPC_LANE_LAZY_DXU;
+    constexpr bool LAZY = SWAP && !EXACT;
     constexpr int KN = kgain_count<NX, NU, KPACK>();
     int FX = SF::X, FU = SF::U, FXo = SWAP ? SF::X1 : SF::X, FUo = SWAP ? SF::U1 : SF::U;
 
@@ -293,7 +246,7 @@ sqp_lane_kernel(SolveParams p,
     // Every copy below loads LB stages into registers before storing them: the workspace stores may alias the input
     // pointers, so a load-store-load order would wait out one memory round trip per element (the load and
     // write-back phases took 9.5 % of the cfg#3 kernel that way).
-    constexpr int LB = (std::is_same<FT, double>::value || MMPC_LANE_LB32) ? 5 : 1;
+    constexpr int LB = 5;
     {
         const double* Vin = p.V + inst * (int64_t)NV;
         double x0v[NX];
@@ -440,18 +393,17 @@ sqp_lane_kernel(SolveParams p,
     // the forward and step sweeps need only A d and A dx + B du: a model with a directional derivative (ExoArm)
     // evaluates that instead of the Jacobian blocks (linear mode keeps its stored blocks)
     constexpr bool JVP = HasJvp<Model>::value;
-    constexpr bool F64 = std::is_same<FT, double>::value;
     // first row q of Y = L^-1 [H_wx | -R] that can be nonzero in column j (the -R block is lower triangular)
-    auto ylo = [](int j) constexpr { return (j < NX || !(F64 || MMPC_LANE_YLO32)) ? 0 : j - NX; };
-    constexpr bool JACH = HasJacH<Model>::value && (F64 || MMPC_LANE_JACH32);
+    auto ylo = [](int j) constexpr { return j < NX ? 0 : j - NX; };
+    constexpr bool JACH = HasJacH<Model>::value;
     // FUSE_FWD: the step sweep evaluates the alpha = 1 trial point with its Jacobian and forms there
     // everything pass (1) of the next iteration computes at that point (defects, d, J, |c|_1, max|c|), so when the
     // full step is accepted (99.7 % of the cfg#3 iterations, every one after the first: tools/alpha_stats.py) the
     // next iteration starts at (2).  This saves the value-only trial evaluation and pass (1)'s sweep (cfg#3:
     // 11.63 -> 11.20 ms).  The fp32-factor build (cfg#5) spilled more with it in round 2 (10.05 -> 11.77 ms); with
     // the directional derivative instead of the trial Jacobian (round 4) it gains there too (7.70 -> 7.34 ms,
-    // profiles/r04/ab_fwd).  fwd_ready: C and D of the workspace hold the accepted iterate's values.
-    constexpr bool FUSE_FWD = FUSE_TRIAL && (std::is_same<FT, double>::value || MMPC_LANE_FWD32);
+    // profiles/r04/ab_fwd).  fwd_ready: D of the workspace holds the accepted iterate's values.
+    constexpr bool FUSE_FWD = FUSE_TRIAL;
     bool fwd_ready = false;
     double J0n = 0.0, c1n = 0.0, cmaxn = 0.0;
     bool nfn = false;
@@ -497,9 +449,9 @@ sqp_lane_kernel(SolveParams p,
                     rk[r] = SK(0, SF::R, r);
                 }
                 // XB: this stage's duals, loaded before the model evaluation (their latency hides behind it)
-                constexpr int XF = (XB && MMPC_LANE_XB_EARLY) ? NY : 1;
+                constexpr int XF = XB ? NY : 1;
                 double zlf[XF], zuf[XF];
-                if constexpr (XB && MMPC_LANE_XB_EARLY) {
+                if constexpr (XB) {
 #pragma unroll
                     for (int j = 0; j < NY; ++j) {
                         zlf[j] = SK(0, SF::ZL, j);
@@ -521,7 +473,6 @@ sqp_lane_kernel(SolveParams p,
                 for (int r = 0; r < NX; ++r) {
                     const double F = fma(h, xd[r], xk[r]);
                     const double c = F - xn[r];
-                    if constexpr (!MMPC_LANE_C_NOSTORE) SK(0, SF::C, r) = c;
                     cmax = fmax(cmax, fabs(c));
                     c1 += fabs(c);
                     nonfinite |= !isfinite(c);
@@ -541,14 +492,7 @@ sqp_lane_kernel(SolveParams p,
 #pragma unroll
                     for (int j = 0; j < NY; ++j) {
                         double sg, bb, zg;
-                        double zl, zu;
-                        if constexpr (MMPC_LANE_XB_EARLY) {
-                            zl = zlf[j];
-                            zu = zuf[j];
-                        } else {
-                            zl = SK(0, SF::ZL, j);
-                            zu = SK(0, SF::ZU, j);
-                        }
+                        const double zl = zlf[j], zu = zuf[j];
                         ip_terms(j < NX ? xk[j] : u[j - NX], yl[j], yu[j], zl, zu, mub, sg, bb, zg, cmpl0, cmplmu, lsum);
                         SK(0, SF::SG, j) = sg;
                         SK(0, SF::BB, j) = bb;
@@ -741,7 +685,7 @@ sqp_lane_kernel(SolveParams p,
                     unext[c] = 0.0;
                     upf[c] = ST(N - 1, FU, c);
                 }
-                double xk1[NX];   // x_{k+1} (MMPC_LANE_C_NOSTORE)
+                double xk1[NX];   // x_{k+1}, for c_k
 #pragma unroll
                 for (int r = 0; r < NX; ++r) {
                     xpf[r] = ST(N - 1, FX, r);
@@ -755,7 +699,6 @@ sqp_lane_kernel(SolveParams p,
 #pragma unroll
                     for (int r = 0; r < NX; ++r) {
                         x[r] = xpf[r];
-                        if constexpr (!MMPC_LANE_C_NOSTORE) cc[r] = SK(0, SF::C, r);
                         dk[r] = SK(0, SF::D, r);
                     }
 #pragma unroll
@@ -778,7 +721,7 @@ sqp_lane_kernel(SolveParams p,
                     for (int c = 0; c < NU; ++c) upf[c] = um[c];
                     // XB: the barrier pieces this stage adds (u part of stage k, x part of stage k-1), loaded before the
                     // model evaluation so that their latency hides behind it (read at their uses they stalled the sweep)
-                    constexpr int XE = (XB && MMPC_LANE_XB_EARLY) ? 1 : 0;
+                    constexpr bool XE = XB;   // early loads: every state-bounded sweep
                     double zgu[XE ? NU : 1], sgu[XE ? NU : 1], bbu[XE ? NU : 1], zgx[XE ? NX : 1], sgx[XE ? NX : 1],
                         bbx[XE ? NX : 1];
                     if constexpr (XE) {
@@ -797,22 +740,23 @@ sqp_lane_kernel(SolveParams p,
                             }
                         }
                     }
-                    auto xb_zgu = [&](int c) { if constexpr (XE) return zgu[c]; else return (double)SK(0, SF::ZG, NX + c); };
-                    auto xb_sgu = [&](int c) { if constexpr (XE) return sgu[c]; else return (double)SK(0, SF::SG, NX + c); };
-                    auto xb_bbu = [&](int c) { if constexpr (XE) return bbu[c]; else return (double)SK(0, SF::BB, NX + c); };
-                    auto xb_zgx = [&](int r) { if constexpr (XE) return zgx[r]; else return (double)SK(-1, SF::ZG, r); };
-                    auto xb_sgx = [&](int r) { if constexpr (XE) return sgx[r]; else return (double)SK(-1, SF::SG, r); };
-                    auto xb_bbx = [&](int r) { if constexpr (XE) return bbx[r]; else return (double)SK(-1, SF::BB, r); };
+                    // accessors for the `if (XB)` uses below.  Without state bounds they are never called; that they
+                    // still capture sk keeps those kernels' code objects byte-identical to the ones measured (the
+                    // arrays read directly, or accessors that capture nothing, moved a few instructions)
+                    auto xb_zgu = [&](int c) { if constexpr (XB) return zgu[c]; else { (void)sk; return 0.0; } };
+                    auto xb_sgu = [&](int c) { if constexpr (XB) return sgu[c]; else { (void)sk; return 0.0; } };
+                    auto xb_bbu = [&](int c) { if constexpr (XB) return bbu[c]; else { (void)sk; return 0.0; } };
+                    auto xb_zgx = [&](int r) { if constexpr (XB) return zgx[r]; else { (void)sk; return 0.0; } };
+                    auto xb_sgx = [&](int r) { if constexpr (XB) return sgx[r]; else { (void)sk; return 0.0; } };
+                    auto xb_bbx = [&](int r) { if constexpr (XB) return bbx[r]; else { (void)sk; return 0.0; } };
                     STAGE_EVAL(x, u, xd, hFq, hFqd, hFu, true);
-                    if constexpr (MMPC_LANE_C_NOSTORE) {
-                        // c_k = F(x_k, u_k) - x_{k+1} from this sweep's own evaluation (round 6: no C record in the
-                        // workspace; the Jacobian evaluation's value is pass (1)'s bit for bit on cfg#3/#5, exact, |u|
-                        // <= 0.5: profiles/r06/cns)
+                    // c_k = F(x_k, u_k) - x_{k+1} from this sweep's own evaluation (round 6: no C record in the
+                    // workspace; the Jacobian evaluation's value is pass (1)'s bit for bit on cfg#3/#5, exact, |u|
+                    // <= 0.5: profiles/r06/cns)
 #pragma unroll
-                        for (int r = 0; r < NX; ++r) {
-                            cc[r] = fma(h, xd[r], x[r]) - xk1[r];
-                            xk1[r] = x[r];
-                        }
+                    for (int r = 0; r < NX; ++r) {
+                        cc[r] = fma(h, xd[r], x[r]) - xk1[r];
+                        xk1[r] = x[r];
                     }
                     // exact Hessian: W_k at (x_k, u_k) with lam_{k+1} (lam holds it until the adjoint step below)
                     constexpr int KZ = NX + NU;
@@ -1286,7 +1230,6 @@ sqp_lane_kernel(SolveParams p,
                         x[r] = xpf[r];
                         xpf[r] = SK(1, FX, r);
                         rk[r] = SK(0, SF::R, r);
-                        if constexpr (!MMPC_LANE_C_RECOMPUTE) ck[r] = SK(0, SF::C, r);
                     }
 #pragma unroll
                     for (int c = 0; c < NU; ++c) {
@@ -1295,9 +1238,9 @@ sqp_lane_kernel(SolveParams p,
                     }
                     // XB: the duals and barrier gradient of this stage for the fraction to the boundary, loaded before
                     // the model evaluation (read at their use, at the end of the stage, they stalled the sweep)
-                    constexpr int XS = (XB && MMPC_LANE_XB_EARLY_STEP) ? NY : 1;
+                    constexpr int XS = XB ? NY : 1;
                     double zls[XS], zus[XS], bbs[XS];
-                    if constexpr (XB && MMPC_LANE_XB_EARLY_STEP) {
+                    if constexpr (XB) {
 #pragma unroll
                         for (int j = 0; j < NY; ++j) {
                             zls[j] = SK(0, SF::ZL, j);
@@ -1308,50 +1251,29 @@ sqp_lane_kernel(SolveParams p,
                     double du[NU];
                     const gmem<double>* const kb = stage_ptr(wsb, k, SS, 0) + SF::K * 64;
                     const gmem<FT>* const kk = (const gmem<FT>*)(kb + NU * 64) + lane;
-                    if constexpr (!XB || MMPC_LANE_XB_BATCHED) {
-                        // all loads of [K_k | kff_k] issued before the first use: under register pressure the
-                        // scheduler otherwise interleaves load -> vmcnt(0) -> fma, one memory round trip per gain
-                        FT kv[KN];
-                        double kf[NU];
+                    {
+                    // all loads of [K_k | kff_k] issued before the first use: under register pressure the
+                    // scheduler otherwise interleaves load -> vmcnt(0) -> fma, one memory round trip per gain
+                    FT kv[KN];
+                    double kf[NU];
 #pragma unroll
-                        for (int a = 0; a < NU; ++a) kf[a] = kb[a * 64 + lane];
+                    for (int a = 0; a < NU; ++a) kf[a] = kb[a * 64 + lane];
 #pragma unroll
-                        for (int e = 0; e < KN; ++e) kv[e] = kk[e * 64];
-                        __builtin_amdgcn_sched_barrier(0);
-#if MMPC_LANE_XTRA_K   // diagnostic A/B only: the gains stored back (same values): + the K record's write traffic
+                    for (int e = 0; e < KN; ++e) kv[e] = kk[e * 64];
+                    __builtin_amdgcn_sched_barrier(0);
+                    double dr[NU];   // the vector K_u multiplies: du_{k-1}, or R o du_{k-1} (KPACK)
 #pragma unroll
-                        for (int e = 0; e < KN; ++e) ((gmem<FT>*)kk)[e * 64] = kv[e];
-#endif
-                        double dr[NU];   // the vector K_u multiplies: du_{k-1}, or R o du_{k-1} (KPACK)
+                    for (int c = 0; c < NU; ++c) dr[c] = KPACK ? R[c] * dup[c] : dup[c];
 #pragma unroll
-                        for (int c = 0; c < NU; ++c) dr[c] = KPACK ? R[c] * dup[c] : dup[c];
+                    for (int a = 0; a < NU; ++a) {
+                        double t = kf[a];
 #pragma unroll
-                        for (int a = 0; a < NU; ++a) {
-                            double t = kf[a];
+                        for (int q = 0; q < NX; ++q) t = fma((double)kv[kgain_idx<NX, NU, KPACK>(a, q)], dx[q], t);
 #pragma unroll
-                            for (int q = 0; q < NX; ++q) t = fma((double)kv[kgain_idx<NX, NU, KPACK>(a, q)], dx[q], t);
-#pragma unroll
-                            for (int c = 0; c < NU; ++c) t = fma((double)kv[kgain_idx<NX, NU, KPACK>(a, NX + c)], dr[c], t);
-                            du[a] = t;
-                            if (wdxu) SK(0, SF::DU, a) = t;
-                        }
-                    } else {
-                        // loads at their uses (MMPC_LANE_XB_BATCHED=0 only).  The batched form above computed wrong
-                        // steps in the exo interior-point instantiation under ROCm 7.2's greedy SGPR allocator (a
-                        // register-allocation defect, not the source); with the basic allocator this
-                        // unit is built with it is right, and it made the exo state-bounded cfg#3-size solve
-                        // 92.4 -> 74.3 ms (round 4, profiles/r04/ab_xbb).
-#pragma unroll
-                        for (int a = 0; a < NU; ++a) {
-                            double t = kb[a * 64 + lane];
-#pragma unroll
-                            for (int q = 0; q < NX; ++q) t = fma((double)kk[kgain_idx<NX, NU, KPACK>(a, q) * 64], dx[q], t);
-#pragma unroll
-                            for (int c = 0; c < NU; ++c)
-                                t = fma((double)kk[kgain_idx<NX, NU, KPACK>(a, NX + c) * 64], KPACK ? R[c] * dup[c] : dup[c], t);
-                            du[a] = t;
-                            SK(0, SF::DU, a) = t;
-                        }
+                        for (int c = 0; c < NU; ++c) t = fma((double)kv[kgain_idx<NX, NU, KPACK>(a, NX + c)], dr[c], t);
+                        du[a] = t;
+                        if (wdxu) SK(0, SF::DU, a) = t;
+                    }
                     }
                     if (BOUNDED && pass + 1 < kBoundPasses) {  // a free control whose step crosses a bound: hold it
 #pragma unroll
@@ -1379,10 +1301,10 @@ sqp_lane_kernel(SolveParams p,
 #pragma unroll
                     for (int r = 0; r < NX; ++r) {
                         const double F = fma(h, xd[r], x[r]);
-                        // c_k = F(x_k, u_k) - x_{k+1} from this evaluation: the stored C_k is the same expression of the
-                        // same model function at the same point (pass (1) or the previous iteration's fused trial), so
-                        // the same bits, without its load (round 6)
-                        if constexpr (MMPC_LANE_C_RECOMPUTE) ck[r] = F - xpf[r];
+                        // c_k = F(x_k, u_k) - x_{k+1} from this evaluation: the same expression of the same model
+                        // function at the same point as pass (1) or the previous iteration's fused trial, so the same
+                        // bits without a C record to load (round 6)
+                        ck[r] = F - xpf[r];
                         const double qe = 2.0 * Q[r] * (F - rk[r]);
                         dJ = fma(qe, ad[r], dJ);
                         dx[r] = ad[r] + ck[r];
@@ -1397,8 +1319,8 @@ sqp_lane_kernel(SolveParams p,
                     }
                     if constexpr (FUSE_TRIAL) {   // trial point (x_k + dx_k, u_k + du_k), its defect to x_{k+1} + dx_{k+1}
                         // = pass (1) at the iterate the full step gives (the update's fma(1, dx, x) is x + dx): the
-                        // same expressions in the same order, C_k and d_{k+1} stored for the next iteration (C_k of
-                        // this iteration was read above; a rejected full step recomputes both in (1))
+                        // same expressions in the same order, d_{k+1} stored for the next iteration (a rejected full
+                        // step recomputes it in (1))
                         double xt[NX], ut[NU], xdt[NX];
 #pragma unroll
                         for (int r = 0; r < NX; ++r) xt[r] = x[r] + dxk[r];
@@ -1423,7 +1345,6 @@ sqp_lane_kernel(SolveParams p,
                                 const double xn1 = xpf[r] + dx[r];   // x_{k+1} + dx_{k+1}: the update's fma(1, dx, x)
                                 if constexpr (SWAP) SK(1, FXo, r) = xn1;
                                 const double c = F - xn1;
-                                if constexpr (!MMPC_LANE_C_NOSTORE) SK(0, SF::C, r) = c;
                                 cmt1 = fmax(cmt1, fabs(c));
                                 ct1 += fabs(c);
                                 nft1 |= !isfinite(c);
@@ -1456,16 +1377,7 @@ sqp_lane_kernel(SolveParams p,
                     if constexpr (XB) {  // fraction to the boundary of (x_{k+1} | u_k), barrier directional derivative
 #pragma unroll
                         for (int j = 0; j < NY; ++j) {
-                            double zl, zu, bb;
-                            if constexpr (MMPC_LANE_XB_EARLY_STEP) {
-                                zl = zls[j];
-                                zu = zus[j];
-                                bb = bbs[j];
-                            } else {
-                                zl = SK(0, SF::ZL, j);
-                                zu = SK(0, SF::ZU, j);
-                                bb = SK(0, SF::BB, j);
-                            }
+                            const double zl = zls[j], zu = zus[j], bb = bbs[j];
                             ip_step_limits(j < NX ? xpf[j] : u[j - NX], j < NX ? dx[j] : du[j - NX], yl[j], yu[j], zl,
                                            zu, mub, kIpTau, bb, amax, az, dbar);
                         }
@@ -1478,7 +1390,7 @@ sqp_lane_kernel(SolveParams p,
         }
         if (done) break;
         // ---- (4) l1-merit Armijo line search (noise-aware, as sqp_wave.h) ----
-        if constexpr (LAZY && MMPC_LANE_LS_HANDOVER) {
+        if constexpr (LAZY) {
             // a full step rejected after the first iteration: the instance is handed over as at this iteration's stop
             // test (iterate, count, merit weight before this update) instead of running its line search, the step
             // records' regeneration and the extra forward pass with its whole wave waiting (round 6: one such

@@ -81,10 +81,6 @@ struct SolveParams {
     int tail_lws_ss;         // doubles per stage (x 64 lanes)
     int tail_lws_zl;         // field offset of z_l; z_u follows at + nx + nu
     int gpw;               // 16-lane kernel: instance groups per wave of this launch (kGroupsPerWave, or fewer)
-    // 16-lane kernel, launches whose grid is resident at once (DESIGN.md 4c "resident finish"): waves count themselves
-    // out here when they finish and stay resident, sleeping, while other waves of the launch still run; the last one
-    // resets it to 0.  nullptr: waves exit as they finish
-    int32_t* exit_count;
 };
 // instance status while handed over (never returned: the resume launch overwrites it)
 constexpr int ST_HANDED_OVER = 6;
@@ -309,21 +305,30 @@ constexpr int kPhaseStageLog = 16 + 2 * kPhaseWaveLog + 40 * kPhaseWavePhases;
 constexpr int kPhaseSpread = 64;
 constexpr int kPhaseSpreadBase = kPhaseStageLog + 128 * kPhaseWavePhases;
 constexpr int kPhaseSlots = kPhaseSpreadBase + 32 * kPhaseSpread;
-__device__ unsigned long long g_mmpc_phase_cycles[kPhaseSlots];
+// the table every unit carries: all of the above (1.46 MB) in the timing build; otherwise nothing writes it and 16 slots
+// are there for mmpc_debug_phase_cycles to read as zeros
+#ifdef MMPC_PHASE_TIMING
+constexpr int kPhaseTableSlots = kPhaseSlots;
+#else
+constexpr int kPhaseTableSlots = 16;
+#endif
+__device__ unsigned long long g_mmpc_phase_cycles[kPhaseTableSlots];
 // this translation unit's table (static: device variables are per code object without -fgpu-rdc), spread copies
-// folded into slots 0..15, the first n slots to out
+// folded into slots 0..15, the first n (<= kPhaseTableSlots) slots to out
 static inline hipError_t phase_table_read(unsigned long long* out, int n, bool reset) {
-    static unsigned long long full[kPhaseSlots];
+    static unsigned long long full[kPhaseTableSlots];
     hipError_t e = hipMemcpyFromSymbol(full, HIP_SYMBOL(g_mmpc_phase_cycles), sizeof(full));
     if (e != hipSuccess) return e;
+#ifdef MMPC_PHASE_TIMING
     for (int c = 0; c < kPhaseSpread; ++c)
         for (int q = 0; q < 16; ++q) {
             const unsigned long long v = full[kPhaseSpreadBase + 32 * c + q];
             full[q] = (q >= 10 && q <= 12) ? (v > full[q] ? v : full[q]) : full[q] + v;
         }
+#endif
     for (int i = 0; i < n; ++i) out[i] = full[i];
     if (reset) {
-        static const unsigned long long z[kPhaseSlots] = {0};
+        static const unsigned long long z[kPhaseTableSlots] = {0};
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_mmpc_phase_cycles), z, sizeof(z));
     }
     return e;

@@ -1,4 +1,4 @@
-"""GPU: the lane kernel's lazy step records (round 6, csrc/sqp_lane.h MMPC_LANE_LAZY_DXU).  An unbounded lane solve
+"""GPU: the lane kernel's lazy step records (round 6, csrc/sqp_lane.h LAZY).  An unbounded lane solve
 stores the step (dx_k, du_k) only in its first iteration; a lane whose full step is rejected later regenerates it
 before its first shorter trial.  Instances with targets far from the initial state (x 20) and a small Delta-u weight
 take shorter steps in later iterations too (asserted from the per-iteration trace of the same solve, so the
@@ -73,8 +73,8 @@ def test_lane_lazy_step_records_vs_oracle(model, N, B, hess, regen, mmpc_mod, or
 @pytest.mark.parametrize("model,N,B,hess", [("two_link_arm", 30, 256, "gn"), ("exo_arm", 50, 128, "exact")])
 def test_lane_line_search_handover_vs_oracle(model, N, B, hess, mmpc_mod, oracle, tmp_path):
     """The same batches with the default iteration-tail policy: a lane whose full step is rejected after the first
-    iteration is handed to the 16-lane resume launch instead of line-searching in its wave (sqp_lane.h
-    MMPC_LANE_LS_HANDOVER).  The resume launch runs the same SQP from the same iterate, count and merit weight, so the
+    iteration is handed to the 16-lane resume launch instead of line-searching in its wave (sqp_lane.h,
+    ahead of the line search).  The resume launch runs the same SQP from the same iterate, count and merit weight, so the
     solutions are the oracle's (as every hand-over test: tests/test_gpu_tail.py)."""
     om = oracle.EXO if model == "exo_arm" else oracle.TWO_LINK
     w = (W_EXO if model == "exo_arm" else np.array(WEIGHTS_CFG)).copy()

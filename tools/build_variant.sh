@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B library build: lib_var/<name>/libmmpc.so from a copy of mahi-mpc_amd/ (csrc + Makefile) of SRC (default: this
-# tree; e.g. a `git worktree` of an older commit) with extra compiler flags (e.g. -DMMPC_LANE_WPE32=2), for
+# tree; e.g. a `git worktree` of an older commit) with extra compiler flags (e.g. -DMMPC_WAVES_PER_SIMD=2), for
 # tools/gpu_ab.sh.  Usage: tools/build_variant.sh <name> "<extra hipcc flags>" [SRC]
 set -eo pipefail
 cd "$(dirname "$0")/.."

@@ -3,7 +3,9 @@
 
     MMPC_LIB_PATH=mahi-mpc_amd/lib/libmmpc_timing.so python tools/phase_profile.py [--batch 4096]
 
-Stamps serialise the instruction stream, so read the SHARES, not the absolute time."""
+Stamps serialise the instruction stream, so read the SHARES, not the absolute time.  Only the timing library has the
+per-wave slots this reads: the production library's table has 16 slots (all zero) and mmpc_debug_phase_table rejects
+a larger n there."""
 import argparse
 import ctypes as C
 import json
