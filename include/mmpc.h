@@ -199,6 +199,25 @@ int mmpc_set_opts(mmpc_handle* h, const mmpc_opts* opts);
 int mmpc_set_state_bounds(mmpc_handle* h, const double* x_lb, const double* x_ub);
 int mmpc_get_state_bounds(const mmpc_handle* h, double* x_lb, double* x_ub);
 
+/* Barrier-parameter rule of the interior point, i.e. of the solves with finite state bounds; every other solve ignores
+ * it.  MONOTONE (the default): IPOPT's monotone rule, mu lowered when the barrier problem's error falls under
+ * 10 mu.  MEHROTRA: Mehrotra's predictor-corrector -- each iteration solves its stage QPs twice with one set of
+ * matrices (affine predictor, then a corrector with mu_t = (mu_aff / mu)^3 mu and the second-order terms), reaching the
+ * same KKT points in about a third fewer iterations (cfg#2 shape, |qdot| <= 1.5, B = 4096: 9.1 mean / 20 max against
+ * 13.4 / 29).  Measured on one MI355X it is nevertheless the SLOWER rule on that line: 2.11 ms against 1.50 ms per
+ * batch with the Gauss-Newton Hessian (1.41x), 1.83 against 1.61 ms with the exact Hessian (1.14x) -- each iteration
+ * costs about 1.5x.  MONOTONE is the faster rule on every line measured; MEHROTRA is opt-in.
+ * Scope of MEHROTRA: the 16-lane solver (MMPC_KKT_RICCATI_GROUP, models with nx + nu < 16) in nonlinear mode, both
+ * Hessians.  A state-bounded solve that resolves to the lane solver (MMPC_KKT_RICCATI, asked for or picked by AUTO)
+ * or runs a linear-mode model returns MMPC_ERR_UNSUPPORTED; it is never run under the other rule.  The rule does not
+ * change what MMPC_KKT_AUTO picks.  mmpc_reserve_workspace reserves for either rule, so setting the rule after a
+ * reservation never makes a solve allocate.  An unknown value: MMPC_ERR_INVALID_ARG (mmpc_last_error names `rule`).
+ * The environment variable MMPC_BARRIER_RULE (0 or 1), read when a handle is created, sets its initial rule
+ * (measurement aid).  Handles of an mmpc_multi: through mmpc_multi_handle. */
+enum mmpc_barrier_rule { MMPC_BARRIER_MONOTONE = 0, MMPC_BARRIER_MEHROTRA = 1 };
+int mmpc_set_barrier_rule(mmpc_handle* h, int32_t rule);
+int mmpc_get_barrier_rule(const mmpc_handle* h, int32_t* rule);
+
 /* Pre-allocate the Riccati solvers' device workspace for batches up to B (so that later
  * stream-ordered solves allocate nothing; the workspace grows on demand otherwise; it includes the iteration-tail
  * hand-over list).  *bytes (may be NULL) receives the workspace size. */

@@ -14,6 +14,9 @@ hipError_t launch_group_two_link(bool exact, dim3 grid, dim3 block, size_t lds, 
 // control-bounded (BOUNDED) and state-bounded (xb, interior point) solves (build/group_two_link_bounded.o)
 hipError_t launch_group_two_link_bounded(bool xb, bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                                          const SolveParams& p, const GroupWork& gwk);
+// state-bounded solves under Mehrotra's predictor-corrector barrier rule (build/group_two_link_bounded.o)
+hipError_t launch_group_two_link_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                                          const SolveParams& p, const GroupWork& gwk);
 // the phase-timing tables of those units (diagnostic build; mmpc_debug_phase_cycles adds them to its own)
 // (the first n <= kPhaseTableSlots slots of the unit's table)
 hipError_t group_two_link_phase_cycles(unsigned long long* out16, int n, bool reset);

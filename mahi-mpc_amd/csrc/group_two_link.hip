@@ -3,7 +3,8 @@
 //   * build/group_two_link.o: the UNBOUNDED kernels (Gauss-Newton and exact Hessian, the cfg#2 path) with LLVM's
 //     default (greedy) register allocators -- they allocate without VGPR spills or scratch (tests/test_build_flags.py
 //     checks the built code object's metadata), and run ~1 % faster than with the basic SGPR allocator;
-//   * build/group_two_link_bounded.o (-DMMPC_GROUP_BOUNDED_UNIT): the control-bounded and state-bounded kernels with
+//   * build/group_two_link_bounded.o (-DMMPC_GROUP_BOUNDED_UNIT): the control-bounded and state-bounded kernels (the
+//     latter under both barrier rules: sqp_group_kernel and sqp_group_mehrotra_kernel) with
 //     -mllvm -sgpr-regalloc=basic like every other unit: they reach the 512-register limit with VGPR spills to
 //     scratch, the profile of the greedy-allocator miscompiles of DESIGN.md 4b.
 #include <hip/hip_runtime.h>
@@ -26,6 +27,20 @@ hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const S
     k<<<grid, block, lds, stream>>>(p, gwk);
     return hipGetLastError();
 }
+#ifdef MMPC_GROUP_BOUNDED_UNIT
+// the interior point under Mehrotra's predictor-corrector rule (mmpc_set_barrier_rule)
+template <bool EXACT>
+hipError_t launch_mehrotra(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
+    auto* k = sqp_group_mehrotra_kernel<TwoLinkArm, EXACT>;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    k<<<grid, block, lds, stream>>>(p, gwk);
+    return hipGetLastError();
+}
+#endif
 // this translation unit's copy of the phase-timing table (as lane_kernels.hip)
 hipError_t unit_phase_cycles(unsigned long long* out16, int n, bool reset) { return phase_table_read(out16, n, reset); }
 }  // namespace
@@ -46,6 +61,11 @@ hipError_t launch_group_two_link_bounded(bool xb, bool exact, dim3 grid, dim3 bl
                          : launch<false, true>(grid, block, lds, stream, p, gwk);
     return exact ? launch<true, false, true>(grid, block, lds, stream, p, gwk)
                  : launch<true>(grid, block, lds, stream, p, gwk);
+}
+hipError_t launch_group_two_link_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                                          const SolveParams& p, const GroupWork& gwk) {
+    return exact ? launch_mehrotra<true>(grid, block, lds, stream, p, gwk)
+                 : launch_mehrotra<false>(grid, block, lds, stream, p, gwk);
 }
 hipError_t group_two_link_bounded_phase_cycles(unsigned long long* out16, int n, bool reset) {
     return unit_phase_cycles(out16, n, reset);

@@ -86,6 +86,8 @@ struct mmpc_handle {
     // state bounds of x_1..x_N (JSON x_min/x_max, or mmpc_set_state_bounds); copied into each launch's arguments
     double x_lb[16], x_ub[16];
     bool x_bounded = false;
+    // barrier rule of the interior point (mmpc_set_barrier_rule, MMPC_BARRIER_RULE at creation); read with the bounds
+    int barrier_rule = MMPC_BARRIER_MONOTONE;
     std::mutex xb_mu;
 };
 
@@ -635,9 +637,12 @@ size_t workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B, bool xb = t
            static_cast<size_t>(blocks) * sizeof(double);
 }
 
-size_t group_workspace_bytes(const mmpc_model_info& mi, int64_t B) {   // the largest variant's (bounded or xb)
+// the largest variant's: bounded, or xb under Mehrotra's rule -- whichever barrier rule the handle has now, so that
+// mmpc_set_barrier_rule after a reservation never makes a solve grow the workspace
+size_t group_workspace_bytes(const mmpc_model_info& mi, int64_t B) {
     const int nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes;
-    const int per = std::max(group_ws_doubles(nx, nu, N, true, false), group_ws_doubles(nx, nu, N, false, true));
+    const int per = std::max(group_ws_doubles(nx, nu, N, true, false),
+                             group_ws_doubles(nx, nu, N, false, true, false, true));
     return static_cast<size_t>(per) * static_cast<size_t>(B) * sizeof(double);
 }
 size_t group_lds_bytes(const mmpc_model_info& mi, int nq, bool bounded = true, bool xb = false) {
@@ -767,6 +772,33 @@ int dispatch_group(bool ub, bool xb, bool exact, dim3 grid, dim3 block, size_t l
     }
 }
 
+// the interior point under Mehrotra's predictor-corrector rule (sqp_group_mehrotra_kernel): state-bounded solves of the
+// models on the lane-distributed path (nx + nu < 16)
+template <class M>
+int dispatch_group_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p,
+                            GroupWork gwk) {
+    if constexpr (std::is_same<M, TwoLinkArm>::value) {
+        const hipError_t e = launch_group_two_link_mehrotra(exact, grid, block, lds, stream, p, gwk);
+        return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string("group kernel launch: ") + hipGetErrorString(e));
+    } else if constexpr (M::NX + M::NU < kGroupLanes) {
+        if constexpr (exact_capable<M>()) {
+            if (exact) {
+                const int rc = set_dynamic_lds(sqp_group_mehrotra_kernel<M, true>, lds);
+                if (rc) return rc;
+                sqp_group_mehrotra_kernel<M, true><<<grid, block, lds, stream>>>(p, gwk);
+                return MMPC_OK;
+            }
+        }
+        const int rc = set_dynamic_lds(sqp_group_mehrotra_kernel<M, false>, lds);
+        if (rc) return rc;
+        sqp_group_mehrotra_kernel<M, false><<<grid, block, lds, stream>>>(p, gwk);
+        return MMPC_OK;
+    } else {
+        return fail(MMPC_ERR_UNSUPPORTED, "barrier rule MEHROTRA: the 16-lane solver runs it for models with "
+                                          "nx + nu < 16 only");
+    }
+}
+
 // Riccati workspace (sqp_lane.h / sqp_group.h layouts), grown on demand.  Growth is synchronous:
 // hipFree waits for the kernels still using the old buffer.
 int ensure_workspace_bytes(mmpc_handle* h, size_t bytes, double** out) {
@@ -796,7 +828,8 @@ int ensure_workspace(mmpc_handle* h, int64_t B, LaneWork* lw) {
     return ensure_workspace_bytes(h, solver_workspace_bytes(h, B) + kTailBytes, &lw->ws);
 }
 
-int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream);
+int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
+                  int barrier_rule = MMPC_BARRIER_MONOTONE);
 
 // Iteration-tail hand-over of a lane-kernel solve: the lane kernel's wave runs until its slowest lane
 // converges (cfg#3: 1 % of the instances need a 5th iteration, and the waves holding them set the kernel time), so
@@ -912,8 +945,10 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     // any bound pointer selects the kernels' BOUNDED variant (projected GN-SQP, sqp_wave.h); host entry
     // points pass NULL for bounds that are all infinite
     const bool bounded = u_lb || u_ub;
+    int barrier_rule;
     {  // state bounds: the interior-point variant (sqp_wave.h "state bounds"), by value in the launch arguments
         std::lock_guard<std::mutex> lk(h->xb_mu);
+        barrier_rule = h->barrier_rule;
         p.x_bounded = h->x_bounded;
         for (int i = 0; i < 16; ++i) {
             p.x_lb[i] = i < mi.num_x ? h->x_lb[i] : -INFINITY;
@@ -921,14 +956,26 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
         }
     }
     const int solver = resolve_kkt_solver(h, B);
-    return launch_kernel(h, solver, p, bounded, stream);
+    return launch_kernel(h, solver, p, bounded, stream, barrier_rule);
 }
 
 // one kernel launch for solver (not AUTO) on p.B instances
-int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream) {
+int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
+                  int barrier_rule) {
     const mmpc_model_info& mi = h->info;
     const int64_t B = p.B;
     const int N = mi.num_shooting_nodes;
+    // the barrier rule matters to the interior point alone (finite state bounds); Mehrotra's rule is built into the
+    // 16-lane kernel for nonlinear solves -- anything else is refused, never run under the other rule
+    const bool mehr = p.x_bounded != 0 && barrier_rule == MMPC_BARRIER_MEHROTRA;
+    if (mehr && mi.is_linear)
+        return fail(MMPC_ERR_UNSUPPORTED, "barrier rule MEHROTRA: not available in linear mode "
+                                          "(use MMPC_BARRIER_MONOTONE)");
+    if (mehr && solver != MMPC_KKT_RICCATI_GROUP)
+        return fail(MMPC_ERR_UNSUPPORTED,
+                    std::string("barrier rule MEHROTRA: needs the 16-lane solver (MMPC_KKT_RICCATI_GROUP), this solve ") +
+                        (h->opts.kkt_solver == MMPC_KKT_AUTO ? "resolves to" : "asks for") +
+                        (solver == MMPC_KKT_RICCATI ? " the lane solver (MMPC_KKT_RICCATI)" : " the condensed solver"));
     if (solver == MMPC_KKT_RICCATI_GROUP) {
         if (h->opts.factor_fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 needs the lane Riccati solver");
         const bool xb = p.x_bounded != 0;
@@ -943,6 +990,8 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
         if (hess < 0) return hess;
         rc = with_model(mi.model_id, [&](auto* m) {
             using M = std::remove_pointer_t<decltype(m)>;
+            if (mehr)
+                return dispatch_group_mehrotra<M>(hess == MMPC_HESSIAN_EXACT, grid, block, lds, stream, p, gwk);
             return dispatch_group<M>(bounded && !xb, xb, hess == MMPC_HESSIAN_EXACT, grid, block, lds, stream, p, gwk,
                                      "group kernel launch");
         });
@@ -1105,6 +1154,11 @@ int mmpc_create_from_json(const char* json_text, const mmpc_opts* opts, mmpc_han
         const long v = std::strtol(e, &end, 10);
         if (end != e && v >= 0 && v <= 64) h->tail_wave_env = static_cast<int>(v);
     }
+    if (const char* e = std::getenv("MMPC_BARRIER_RULE")) {   // measurement: the rule without a change of the caller
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && (v == MMPC_BARRIER_MONOTONE || v == MMPC_BARRIER_MEHROTRA)) h->barrier_rule = static_cast<int>(v);
+    }
     if (const char* e = std::getenv("MMPC_TAIL_ROUNDS")) {
         char* end = nullptr;
         const long v = std::strtol(e, &end, 10);
@@ -1174,6 +1228,21 @@ int mmpc_get_state_bounds(const mmpc_handle* h, double* x_lb, double* x_ub) {
         x_lb[i] = h->x_lb[i];
         x_ub[i] = h->x_ub[i];
     }
+    return MMPC_OK;
+}
+
+int mmpc_set_barrier_rule(mmpc_handle* h, int32_t rule) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (rule != MMPC_BARRIER_MONOTONE && rule != MMPC_BARRIER_MEHROTRA)
+        return fail(MMPC_ERR_INVALID_ARG, "rule: not an mmpc_barrier_rule value (" + std::to_string(rule) + ")");
+    std::lock_guard<std::mutex> lk(h->xb_mu);
+    h->barrier_rule = rule;
+    return MMPC_OK;
+}
+
+int mmpc_get_barrier_rule(const mmpc_handle* h, int32_t* rule) {
+    if (!h || !rule) return fail(MMPC_ERR_INVALID_ARG, "null argument");
+    *rule = h->barrier_rule;
     return MMPC_OK;
 }
 

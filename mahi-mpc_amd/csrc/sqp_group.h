@@ -15,7 +15,20 @@
 // (cross-lane data).  The gains K_k | kff_k go through a per-instance HBM workspace.  The exact-Hessian blocks W_k go
 // there too, except in the unbounded solve of a model with a packed W record (WPack; the 2-link arm, cfg#2): its
 // records stay in LDS, over d / lam, dx and du, which are dead from the W pass to the step sweep.
-#pragma once
+// This header includes itself once: the kernel body below is one text compiled into two __global__ templates (the
+// kernels of the monotone barrier rule and sqp_group_mehrotra_kernel, at the end of the file), so that the former keep
+// exactly the code they had before the second existed.  MMPC_GROUP_PASS: 1 = the whole header (first include), 2 = the
+// body alone (the include inside sqp_group_mehrotra_kernel), 0 = a repeated include (nothing).
+#undef MMPC_GROUP_PASS
+#if defined(MMPC_GROUP_BODY_ONLY)
+#define MMPC_GROUP_PASS 2
+#elif !defined(MMPC_SQP_GROUP_H)
+#define MMPC_SQP_GROUP_H
+#define MMPC_GROUP_PASS 1
+#else
+#define MMPC_GROUP_PASS 0
+#endif
+#if MMPC_GROUP_PASS == 1
 #include <type_traits>
 
 #include "models.h"
@@ -94,10 +107,15 @@ __host__ __device__ constexpr int group_hess_doubles(int nx, int nu) { return nx
 // (x_{k+1} | u_k) after the W blocks, in place of the bounded solves' rows.
 // w_onchip (the unbounded exact-Hessian kernel of a model with a packed W record, WPack): the W blocks stay in LDS, so
 // the kernel strides instances by K | kff alone (420 doubles at cfg#2).
+// mehr (the xb variant under Mehrotra's predictor-corrector rule): the per-bound corrector terms of (x_{k+1} | u_k),
+// lower and upper, follow the xb fields; then per stage the record the predictor's Riccati sweep leaves for the
+// corrector's vector-only sweep: 2 + nu doubles per lane (P~_x c, the b-independent part of p~, L^-1 [H_wx | -R]) and
+// the Cholesky factor of H_ww with the b-independent part of h_w, once.
 __host__ __device__ constexpr int group_ws_doubles(int nx, int nu, int N, bool bounded = true, bool xb = false,
-                                                  bool w_onchip = false) {
+                                                  bool w_onchip = false, bool mehr = false) {
     return N * nu * (nx + nu + 1) + (w_onchip ? 0 : N * group_hess_doubles(nx, nu)) +
-           (bounded ? N * nu * (nx + 2 * nu + 1) : 0) + (xb ? 5 * N * (nx + nu) : 0);
+           (bounded ? N * nu * (nx + 2 * nu + 1) : 0) + (xb ? 5 * N * (nx + nu) : 0) +
+           (mehr ? 2 * N * (nx + nu) + N * ((2 + nu) * kGroupLanes + nu * (nu + 1) / 2 + nu) : 0);
 }
 // the cfg#2 shape (2-link arm, N = 30, unbounded): four instances per workgroup within 40,960 B of LDS, so that four
 // workgroups (one per SIMD) fit a CU -- the on-chip W record lives in arrays that are dead while it is alive and adds
@@ -193,9 +211,21 @@ __device__ __forceinline__ void group_model(bool lin, const double* lFq, const d
 // second derivatives on the lane-distributed path: unbounded, control-bounded (held controls fixed in the exact QP)
 // and, round 6, state-bounded (W_k joins the barrier-augmented stage blocks; oracle solve_one_ip with the exact
 // Hessian).
+// MEHR (XB only): Mehrotra's predictor-corrector barrier rule (mmpc_set_barrier_rule; oracle solve_one_ip, rule 1) in
+// place of the monotone update.  Each iteration solves the stage QPs twice with one set of matrices: the affine
+// predictor (barrier gradient b = 0) gives the step to the boundary, from which the target mu_t = sigma mu with
+// sigma = (mu_aff / mu)^3 and the per-bound second-order terms -ds_aff dz_aff follow; the corrector solves with
+// b = -(mu_t - ds dz)_l / s_l + (mu_t - ds dz)_u / s_u.  Dual steps, merit and the kappa_Sigma safeguard use mu_t and
+// the corrected terms; there is no lagged update.  Every MEHR statement sits behind `if constexpr`, and the kernels
+// of the monotone rule are sqp_group_kernel's, with their names and code unchanged.
+// The body is shared with sqp_group_mehrotra_kernel (end of the file), which sets BOUNDED = false, XB = true, MEHR = true.
 template <class Model, bool BOUNDED = false, bool XB = false, bool EXACT = false>
 __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork gw) {
+    constexpr bool MEHR = false;
+#endif  // MMPC_GROUP_PASS == 1
+#if MMPC_GROUP_PASS != 0   // ---- the kernel body: Model, BOUNDED, XB, EXACT, MEHR, p, gw in scope ----
     static_assert(!(BOUNDED && XB), "the interior-point variant handles the control bounds itself");
+    static_assert(!MEHR || XB, "the barrier rule belongs to the interior-point variant");
     constexpr int NX = Model::NX, NU = Model::NU, NQ = Model::NQ, NA = NX - NQ, NS = NX + NU, ND = NX + NU;
     constexpr int SQ = NA * NQ > 0 ? NA * NQ : 1;  // extent of the h da/dq block (empty for NQ = 0)
     constexpr int FQ = NA * NQ, FD = NA * NA, FU = NA * NU;  // stage block sizes (sqp_lane.h a_mul)
@@ -247,7 +277,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // variants solve it again after step sweeps that rewrite sDX, sD and sDU, and keep W in the workspace.
     constexpr int PK = WPack<Model>::PK;
     constexpr bool WLDS = EXACT && !BOUNDED && !XB && IsControlAffine<Model>::value && PK >= NX && PK <= 2 * NX + NU;
-    double* const wK = gw.ws + slot * (int64_t)group_ws_doubles(NX, NU, N, BOUNDED, XB, WLDS);  // [N][NU][NS+1]
+    double* const wK = gw.ws + slot * (int64_t)group_ws_doubles(NX, NU, N, BOUNDED, XB, WLDS, MEHR);  // [N][NU][NS+1]
     constexpr int KZ = NX + NU, HW = group_hess_doubles(NX, NU);
     double* const wH = wK + N * NU * (NS + 1);  // EXACT: [N][HW] = W_k x rows [NX][KZ] | W_k uu block [NU][NU]
     double* const sW = sD + NX;                 // WLDS: [N][PK] packed W_k x rows, over sD[1..], sDX and sDU
@@ -262,6 +292,15 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     double* const sSg = sZu + N * NY;
     double* const sBb = sSg + N * NY;
     double* const sZg = sBb + N * NY;
+    // MEHR: corrector terms mu_t - ds_aff dz_aff of the lower / upper bounds, written and read by the stage's own lane
+    [[maybe_unused]] double* const sCl = sZg + N * NY;   // [N][NY]
+    [[maybe_unused]] double* const sCu = sCl + N * NY;
+    // MEHR: what the predictor's Riccati sweep (backward_dist) leaves per stage for the corrector's vector-only sweep
+    // (backward_vec).  Per lane r [VL][G]: pc = P~_{k+1,x} row r . c_k, pn0 = the b-independent part of row r of p~_k,
+    // Ytil[NU] = column r of L^-1 [H_wx | -R]; once [VS]: L row by row with 1 / L_aa on the diagonal, then the
+    // b-independent part of h_w (bit-identical on every lane: each lane stores and reads them)
+    constexpr int VL = 2 + NU, VC = NU * (NU + 1) / 2, VS = VC + NU, VR = VL * G + VS;
+    [[maybe_unused]] double* const sVr = sCu + N * NY;   // [N][VR]
     const double* const trg = p.traj + ii * (int64_t)N * NX;
 
     const double* w = p.weights + ii * p.w_stride;
@@ -283,6 +322,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     //      (XB) add the barrier terms and use the Cholesky (Y^T Y) form of the stage update.  Models with
     //      nx + nu >= 16 keep the one-lane sweep below. ----
     constexpr bool DIST = (NS < G);
+    static_assert(!MEHR || DIST, "Mehrotra's rule: lane-distributed path");
     // control-affine model: the u-u block of the exact-Hessian W_k is zero -- neither stored, loaded nor added
     constexpr bool CAFF = IsControlAffine<Model>::value;
     static_assert(!EXACT || (DIST && HasHess<Model>::value), "exact Hessian: lane-distributed path, model eval_hess");
@@ -479,7 +519,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     double sg, bb, zg;
                     ip_terms(y, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], mub, sg, bb, zg, cmpl0, cmplmu, lsum);
                     sSg[k * NY + j] = sg;
-                    sBb[k * NY + j] = bb;
+                    if constexpr (MEHR) sBb[k * NY + j] = 0.0;   // the affine predictor's barrier gradient
+                    else sBb[k * NY + j] = bb;
                     sZg[k * NY + j] = zg;
                 }
             }
@@ -1304,6 +1345,22 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                         Kcol[a] = t * il[a];
                         kff[a] = th * il[a];
                     }
+                    if constexpr (MEHR) {   // the record of this stage for backward_vec
+                        double* const rec = sVr + k * VR;
+                        double pc = 0.0;
+#pragma unroll
+                        for (int q = 0; q < NX; ++q) pc = fma(Prow[q], cc[q], pc);
+                        rec[r] = pc;
+                        rec[G + r] = fma(-Rr, duu, lxm * (Qr * exr));
+#pragma unroll
+                        for (int a = 0; a < NU; ++a) {
+                            rec[(2 + a) * G + r] = Ytil[a];
+#pragma unroll
+                            for (int q = 0; q < a; ++q) rec[VL * G + a * (a + 1) / 2 + q] = Ld[a][q];
+                            rec[VL * G + a * (a + 1) / 2 + a] = il[a];
+                            rec[VL * G + VC + a] = fma(R[a], u[a] - um[a], Rm[a] * u[a]);
+                        }
+                    }
                 } else if constexpr (NU == 2) {
                     const double det = fma(Hww[0][0], Hww[1][1], -Hww[0][1] * Hww[0][1]);
                     fact_ok &= (Hww[0][0] > 0.0) && (det > 0.0) && isfinite(det);
@@ -1468,6 +1525,78 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     stage(k - 1, F_{}, w0);
                 }
                 stage(0, std::true_type{}, w0);
+            }
+        };
+        // MEHR corrector: the vector part (p~, kff) of the Riccati recursion for the barrier gradient now in sBb, on the
+        // matrices of the sweep that just ran (its per-stage record sVr): mv = p~ + P~_x c, h_w, kff = H_ww^-1 h_w through
+        // the stored factor, p~_k = pn - Ytil^T L^-1 h_w.  Only the kff column of the gains is rewritten.
+        [[maybe_unused]] auto backward_vec = [&]() {
+            if constexpr (MEHR) {
+                const double lxm = lx ? 1.0 : 0.0;
+                double pvr = Qr * (lx ? sX[N * NX + rx] - tr[(N - 1) * NX + rx] : 0.0);   // Q (x_N - r_{N-1})
+                pvr = fma(lxm, sBb[(N - 1) * NY + rx], pvr);
+                struct Rec {
+                    double pc, pn0, yt[NU], sh[VS], bbu[NU], bbx;
+                };
+                auto fetch = [&](int k, Rec& o) {
+                    const double* const rec = sVr + k * VR;
+                    o.pc = rec[r];
+                    o.pn0 = rec[G + r];
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) {
+                        o.yt[a] = rec[(2 + a) * G + r];
+                        o.bbu[a] = sBb[k * NY + NX + a];
+                    }
+#pragma unroll
+                    for (int i = 0; i < VS; ++i) o.sh[i] = rec[VL * G + i];
+                    o.bbx = sBb[(k > 0 ? k - 1 : 0) * NY + rx];   // b of x_k (stage k - 1's y); unused at k = 0
+                };
+                auto stage = [&](int k, const Rec& o) {
+                    double hFu[FU], acol[NA];
+#pragma unroll
+                    for (int i = 0; i < FU; ++i) hFu[i] = sFu[k * FU + i];
+                    load_acol(k, acol);
+                    const double mv = pvr + o.pc;
+                    double mvb[NS];
+                    sfor<0, NS>([&](auto I) { mvb[I] = row_bcast<I>(mv); });
+                    double htil[NU], kff[NU];
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) {   // h_w, then L^-1 h_w
+                        double t = o.sh[VC + a] + mvb[NX + a];
+#pragma unroll
+                        for (int s2 = 0; s2 < NA; ++s2) t = fma(hFu[s2 * NU + a], mvb[NQ + s2], t);
+                        t += o.bbu[a];
+#pragma unroll
+                        for (int q = 0; q < a; ++q) t = fma(-o.sh[a * (a + 1) / 2 + q], htil[q], t);
+                        htil[a] = t * o.sh[a * (a + 1) / 2 + a];
+                    }
+#pragma unroll
+                    for (int a = NU - 1; a >= 0; --a) {
+                        double t = htil[a];
+#pragma unroll
+                        for (int q = a + 1; q < NU; ++q) t = fma(-o.sh[q * (q + 1) / 2 + a], kff[q], t);
+                        kff[a] = t * o.sh[a * (a + 1) / 2 + a];
+                    }
+                    // bit-identical on every lane: duplicate stores, no exec-mask branch (as backward_dist)
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) wK[(k * NU + a) * (NS + 1) + NS] = -kff[a];
+                    if (k == 0) return;
+                    double pv2 = fma(lxm, colA(mv, acol, mvb) + o.bbx, o.pn0);
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) pv2 = fma(-o.yt[a], htil[a], pv2);
+                    pvr = pv2;
+                };
+                // two buffers, each refilled one stage ahead of its use
+                Rec o0, o1;
+                fetch(N - 1, o0);
+                int k = N - 1;
+                for (; k >= 1; k -= 2) {
+                    fetch(k - 1, o1);
+                    stage(k, o0);
+                    fetch(k >= 2 ? k - 2 : 0, o0);
+                    stage(k - 1, o1);
+                }
+                if (k == 0) stage(0, o0);
             }
         };
         if constexpr (DIST) {
@@ -1735,6 +1864,60 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     }
                 }
             };
+            if constexpr (MEHR) {
+                // affine predictor step (the sweep above ran with b = 0): dy_aff in sDX | sDU
+                step_dist(false);
+                __builtin_amdgcn_wave_barrier();
+                // stage-parallel: steps to the boundary without tau, mu = avg(s z), mu_aff at the end of those steps
+                double ap = 1.0, ad = 1.0, sz = 0.0;
+                for (int k = gl; k < N; k += G) {
+#pragma unroll
+                    for (int j = 0; j < NY; ++j) {
+                        const double y = j < NX ? sX[(k + 1) * NX + j] : sU[k * NU + j - NX];
+                        const double dy = j < NX ? sDX[(k + 1) * NX + j] : sDU[k * NU + j - NX];
+                        ip_aff_limits(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], ap, ad, sz);
+                    }
+                }
+                ap = group_min(ap);
+                ad = group_min(ad);
+                sz = group_sum(sz);
+                double saff = 0.0;
+                for (int k = gl; k < N; k += G) {
+#pragma unroll
+                    for (int j = 0; j < NY; ++j) {
+                        const double y = j < NX ? sX[(k + 1) * NX + j] : sU[k * NU + j - NX];
+                        const double dy = j < NX ? sDX[(k + 1) * NX + j] : sDU[k * NU + j - NX];
+                        saff += ip_aff_compl(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], ap, ad);
+                    }
+                }
+                saff = group_sum(saff);
+                int nb = 0;   // finite bounds of one stage
+#pragma unroll
+                for (int j = 0; j < NY; ++j) nb += (yl[j] > -INFINITY) + (yu[j] < INFINITY);
+                const double mbnd = (double)nb * (double)N;
+                const double muc = sz / mbnd, mua = saff / mbnd;   // XB: at least one finite bound
+                const double sig = muc > 0.0 ? pow(mua / muc, 3.0) : 0.0;
+                // the target mu_t replaces the barrier parameter of this iteration (merit, duals, safeguard, trace)
+                mub = fmax(kIpTolCompl / 20.0, fmin(sig * muc, kIpMu0));
+                for (int k = gl; k < N; k += G) {
+#pragma unroll
+                    for (int j = 0; j < NY; ++j) {
+                        const double y = j < NX ? sX[(k + 1) * NX + j] : sU[k * NU + j - NX];
+                        const double dy = j < NX ? sDX[(k + 1) * NX + j] : sDU[k * NU + j - NX];
+                        double ccl, ccu, bb;
+                        ip_corrector(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], mub, ccl, ccu, bb);
+                        sCl[k * NY + j] = ccl;
+                        sCu[k * NY + j] = ccu;
+                        sBb[k * NY + j] = bb;
+                    }
+                }
+                // the corrected b of every stage visible to the other lanes' sweep
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                // corrector: the same stage matrices and factors with the corrected b -- only the vector part of the
+                // recursion changes (backward_vec); the usual step sweep follows
+                backward_vec();
+            }
             for (int pass = 0;; ++pass) {
                 if (pass > 0) {   // BOUNDED: controls held after the previous step -- solve the QP again
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1803,8 +1986,12 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 for (int j = 0; j < NY; ++j) {
                     const double y = j < NX ? sX[(k + 1) * NX + j] : sU[k * NU + j - NX];
                     const double dy = j < NX ? sDX[(k + 1) * NX + j] : sDU[k * NU + j - NX];
-                    ip_step_limits(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], mub, tau, sBb[k * NY + j],
-                                   amax, az, dbar);
+                    if constexpr (MEHR)
+                        ip_step_limits_pc(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], mub, tau,
+                                          sCl[k * NY + j], sCu[k * NY + j], amax, az, dbar);
+                    else
+                        ip_step_limits(y, dy, yl[j], yu[j], sZl[k * NY + j], sZu[k * NY + j], mub, tau, sBb[k * NY + j],
+                                       amax, az, dbar);
                 }
             }
             amax = group_min(amax);
@@ -1923,13 +2110,16 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     double& y = j < NX ? sX[(k + 1) * NX + j] : sU[k * NU + j - NX];
                     const double dy = j < NX ? sDX[(k + 1) * NX + j] : sDU[k * NU + j - NX];
                     double zl = sZl[k * NY + j], zu = sZu[k * NY + j], yn;
-                    ip_update(y, dy, yl[j], yu[j], zl, zu, mub, alpha, az, yn);
+                    if constexpr (MEHR)
+                        ip_update_pc(y, dy, yl[j], yu[j], zl, zu, mub, sCl[k * NY + j], sCu[k * NY + j], alpha, az, yn);
+                    else
+                        ip_update(y, dy, yl[j], yu[j], zl, zu, mub, alpha, az, yn);
                     y = yn;
                     sZl[k * NY + j] = zl;
                     sZu[k * NY + j] = zu;
                 }
             }
-            mub = mub_next;
+            if constexpr (!MEHR) mub = mub_next;   // MEHR: no lagged update, mu_t is set in every iteration
         } else {
             for (int k = gl; k <= N; k += G) {
                 if (k > 0) {
@@ -1967,6 +2157,19 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     }
     MMPC_PHASE(7);
     MMPC_PHASE_FLUSH
+#endif  // MMPC_GROUP_PASS != 0
+#if MMPC_GROUP_PASS == 1
+}
+
+// the interior-point variant under Mehrotra's predictor-corrector rule (state-bounded solves, nonlinear mode): the
+// body above once more
+template <class Model, bool EXACT = false>
+__global__ __launch_bounds__(64) void sqp_group_mehrotra_kernel(SolveParams p, GroupWork gw) {
+    constexpr bool BOUNDED = false, XB = true, MEHR = true;
+#define MMPC_GROUP_BODY_ONLY
+#include "sqp_group.h"
+#undef MMPC_GROUP_BODY_ONLY
 }
 
 }  // namespace mmpc
+#endif  // MMPC_GROUP_PASS == 1

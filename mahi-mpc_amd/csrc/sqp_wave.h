@@ -224,6 +224,94 @@ __device__ __forceinline__ void ip_update(double y, double dy, double l, double 
         zu = fmax(fmin(zu, kIpKappaSigma * mub / sn), mub / (kIpKappaSigma * sn));
     }
 }
+// ---- Mehrotra's predictor-corrector rule (oracle solve_one_ip, g_ip_rule == 1; the 16-lane kernel's MEHR variant) ----
+// affine predictor step dy (barrier gradient 0): its limits to the boundary, primal and dual, with no tau; sum s z
+__device__ __forceinline__ void ip_aff_limits(double y, double dy, double l, double u, double zl, double zu,
+                                              double& ap, double& ad, double& sz) {
+    if (l > -INFINITY) {
+        const double sl = y - l, dz = -zl - zl / sl * dy;
+        if (dy < 0.0) ap = fmin(ap, -sl / dy);
+        if (dz < 0.0) ad = fmin(ad, -zl / dz);
+        sz += sl * zl;
+    }
+    if (u < INFINITY) {
+        const double su = u - y, dz = -zu + zu / su * dy;
+        if (dy > 0.0) ap = fmin(ap, su / dy);
+        if (dz < 0.0) ad = fmin(ad, -zu / dz);
+        sz += su * zu;
+    }
+}
+// sum (s + ap ds)(z + ad dz) at the end of the affine step
+__device__ __forceinline__ double ip_aff_compl(double y, double dy, double l, double u, double zl, double zu,
+                                               double ap, double ad) {
+    double sa = 0.0;
+    if (l > -INFINITY) {
+        const double sl = y - l, dz = -zl - zl / sl * dy;
+        sa += (sl + ap * dy) * (zl + ad * dz);
+    }
+    if (u < INFINITY) {
+        const double su = u - y, dz = -zu + zu / su * dy;
+        sa += (su - ap * dy) * (zu + ad * dz);
+    }
+    return sa;
+}
+// corrector terms mu_t - ds_aff dz_aff of the lower / upper bound (0 for an infinite bound) and the corrected barrier
+// gradient b = -ccl / s_l + ccu / s_u
+__device__ __forceinline__ void ip_corrector(double y, double dy, double l, double u, double zl, double zu, double mut,
+                                             double& ccl, double& ccu, double& bb) {
+    ccl = 0.0;
+    ccu = 0.0;
+    bb = 0.0;
+    if (l > -INFINITY) {
+        const double sl = y - l, dz = -zl - zl / sl * dy;
+        ccl = -dy * dz + mut;
+        bb -= ccl / sl;
+    }
+    if (u < INFINITY) {
+        const double su = u - y, dz = -zu + zu / su * dy;   // ds_u = -dy
+        ccu = dy * dz + mut;
+        bb += ccu / su;
+    }
+}
+// ip_step_limits with the corrected terms in the dual steps; dbar is the barrier's derivative at mu_t
+__device__ __forceinline__ void ip_step_limits_pc(double y, double dy, double l, double u, double zl, double zu,
+                                                  double mut, double tau, double ccl, double ccu, double& amax,
+                                                  double& az, double& dbar) {
+    double bmu = 0.0;
+    if (l > -INFINITY) {
+        const double sl = y - l;
+        if (dy < 0.0) amax = fmin(amax, -tau * sl / dy);
+        const double dz = ccl / sl - zl - zl / sl * dy;
+        if (dz < 0.0) az = fmin(az, -tau * zl / dz);
+        bmu -= mut / sl;
+    }
+    if (u < INFINITY) {
+        const double su = u - y;
+        if (dy > 0.0) amax = fmin(amax, tau * su / dy);
+        const double dz = ccu / su - zu + zu / su * dy;
+        if (dz < 0.0) az = fmin(az, -tau * zu / dz);
+        bmu += mut / su;
+    }
+    dbar = fma(2.0 * bmu, dy, dbar);
+}
+// ip_update with the corrected terms in the dual steps; the kappa_Sigma safeguard at mu_t
+__device__ __forceinline__ void ip_update_pc(double y, double dy, double l, double u, double& zl, double& zu,
+                                             double mut, double ccl, double ccu, double alpha, double az,
+                                             double& ynew) {
+    ynew = fma(alpha, dy, y);
+    if (l > -INFINITY) {
+        const double sl = y - l;
+        zl += az * (ccl / sl - zl - zl / sl * dy);
+        const double sn = ynew - l;
+        zl = fmax(fmin(zl, kIpKappaSigma * mut / sn), mut / (kIpKappaSigma * sn));
+    }
+    if (u < INFINITY) {
+        const double su = u - y;
+        zu += az * (ccu / su - zu + zu / su * dy);
+        const double sn = u - ynew;
+        zu = fmax(fmin(zu, kIpKappaSigma * mut / sn), mut / (kIpKappaSigma * sn));
+    }
+}
 __device__ __forceinline__ double ip_log_slacks(double y, double l, double u) {
     double lg = 0.0;
     if (l > -INFINITY) lg += log(y - l);

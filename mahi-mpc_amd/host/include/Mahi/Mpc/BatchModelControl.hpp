@@ -66,6 +66,10 @@ public:
     void update_control_limits(std::vector<double> u_min, std::vector<double> u_max);
     // move the warm start k = round((t - t_prev) / step) stages earlier before each solve (default false)
     void set_warm_start_shift(bool on) { m_shift = on; }
+    // barrier rule of the solves with finite state bounds (x_min / x_max of the model file): 0 = IPOPT's monotone rule
+    // (default), 1 = Mehrotra's predictor-corrector (mmpc_set_barrier_rule in include/mmpc.h: 16-lane solver, nonlinear
+    // mode; a solve it does not cover then throws).  Additive: not part of the reference's interface.
+    void set_barrier_rule(int rule);
 
 private:
     struct Impl;

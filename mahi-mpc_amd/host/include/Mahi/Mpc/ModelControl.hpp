@@ -58,6 +58,10 @@ public:
 
     void update_weights(std::vector<double> Q = {}, std::vector<double> R = {}, std::vector<double> Rm = {});
     void update_control_limits(std::vector<double> u_min, std::vector<double> u_max);
+    // barrier rule of the solves with finite state bounds (x_min / x_max of the model file): 0 = IPOPT's monotone rule
+    // (default), 1 = Mehrotra's predictor-corrector (mmpc_set_barrier_rule in include/mmpc.h: 16-lane solver, nonlinear
+    // mode; a solve it does not cover then throws).  Additive: not part of the reference's interface.
+    void set_barrier_rule(int rule);
 
     // ---- build extensions (not in the reference) ----
     // solver status of the last calc_u (the reference ignores IPOPT's status, ModelControl.cpp:159-161)

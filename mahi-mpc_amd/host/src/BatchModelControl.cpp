@@ -366,5 +366,10 @@ void BatchModelControl::update_control_limits(std::vector<double> u_min, std::ve
     model_parameters.u_max = u_max;
 }
 
+void BatchModelControl::set_barrier_rule(int rule) {
+    std::lock_guard<std::mutex> lg(m_solve_mutex);   // between ticks
+    m->check(m->lib->set_barrier_rule(m->h, rule), "mmpc_set_barrier_rule");
+}
+
 }  // namespace mpc
 }  // namespace mahi

@@ -205,5 +205,9 @@ void ModelControl::update_control_limits(std::vector<double> u_min, std::vector<
     model_parameters.u_max = u_max;
 }
 
+void ModelControl::set_barrier_rule(int rule) {
+    m_backend->check(m_backend->set_barrier_rule(m_handle, rule), "mmpc_set_barrier_rule");
+}
+
 }  // namespace mpc
 }  // namespace mahi

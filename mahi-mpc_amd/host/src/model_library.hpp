@@ -27,6 +27,7 @@ struct ModelLibrary {
     decltype(&mmpc_solve_batch_host) solve_batch_host = &mmpc_solve_batch_host;
     decltype(&mmpc_solve_batch) solve_batch = &mmpc_solve_batch;
     decltype(&mmpc_reserve_workspace) reserve_workspace = &mmpc_reserve_workspace;
+    decltype(&mmpc_set_barrier_rule) set_barrier_rule = &mmpc_set_barrier_rule;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
     void* dl = nullptr;  // kept loaded for the process lifetime (HIP code objects), as CasADi keeps its libraries
 
@@ -71,6 +72,7 @@ struct ModelLibrary {
         b->bind(b->solve_batch_host, "mmpc_solve_batch_host");
         b->bind(b->solve_batch, "mmpc_solve_batch");
         b->bind(b->reserve_workspace, "mmpc_reserve_workspace");
+        b->bind(b->set_barrier_rule, "mmpc_set_barrier_rule");
         b->bind(b->last_error, "mmpc_last_error");
         return b;
     }

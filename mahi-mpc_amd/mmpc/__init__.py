@@ -42,6 +42,9 @@ class MmpcError(RuntimeError):
 KKT_AUTO, KKT_CONDENSED, KKT_RICCATI, KKT_RICCATI_GROUP = 0, 1, 2, 3
 INIT_AS_GIVEN, INIT_HOLD_X0, INIT_ZERO = 0, 1, 2
 HESSIAN_AUTO, HESSIAN_GAUSS_NEWTON, HESSIAN_EXACT = 0, 1, 2
+# barrier rule of state-bounded solves (enum mmpc_barrier_rule): IPOPT's monotone rule, or Mehrotra's
+# predictor-corrector (16-lane solver, nonlinear mode; include/mmpc.h)
+BARRIER_MONOTONE, BARRIER_MEHROTRA = 0, 1
 MODEL_TWO_LINK_ARM, MODEL_EXO_ARM, MODEL_USER = 0, 1, 2
 USER_LIB_DIR = os.path.join(ROOT, "lib", "user")
 BUILTIN_MODELS = ("two_link_arm", "double_pendulum", "exo_arm", "exo")  # "mmpc_model" names libmmpc.so serves   # models generated from SX by ModelGenerator (make -C host user)
@@ -126,6 +129,8 @@ def lib(path: str | None = None):
         L.mmpc_resolve_hessian.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
         L.mmpc_set_state_bounds.argtypes = [_vp, _vp, _vp]
         L.mmpc_get_state_bounds.argtypes = [_vp, _vp, _vp]
+        L.mmpc_set_barrier_rule.argtypes = [_vp, C.c_int32]
+        L.mmpc_get_barrier_rule.argtypes = [_vp, C.POINTER(C.c_int32)]
         L.mmpc_status_string.argtypes = [C.c_int32]
         L.mmpc_status_string.restype = C.c_char_p
         L.mmpc_last_error.restype = C.c_char_p
@@ -246,7 +251,7 @@ class Solver:
 
     def __init__(self, model_json=None, json_text=None, max_iter=None, tol_grad=None, tol_defect=None,
                  device=None, kkt_solver=None, factor_fp32=None, library=None, init_states=None, hessian=None,
-                 tail_cap=None, tail_wave_max=None, tail_rounds=None):
+                 tail_cap=None, tail_wave_max=None, tail_rounds=None, barrier_rule=None):
         self._L = L = lib(library or (model_library(model_json) if model_json is not None else None))
         o = Opts()
         L.mmpc_default_opts(C.byref(o))
@@ -284,6 +289,8 @@ class Solver:
         self.nx, self.nu, self.N = info.num_x, info.num_u, info.num_shooting_nodes
         self.NV = info.num_v
         self.h = info.step_size
+        if barrier_rule is not None:
+            self.set_barrier_rule(barrier_rule)
 
     def _check(self, rc):
         _check(rc, self._L)
@@ -369,6 +376,16 @@ class Solver:
         lb, ub = np.zeros(self.nx), np.zeros(self.nx)
         self._check(self._L.mmpc_get_state_bounds(self._h, _ptr(lb), _ptr(ub)))
         return lb, ub
+
+    def set_barrier_rule(self, rule: int):
+        """BARRIER_MONOTONE (default) or BARRIER_MEHROTRA for the solves with finite state bounds (mmpc_set_barrier_rule:
+        MEHROTRA runs on the 16-lane solver in nonlinear mode, other state-bounded solves then raise MmpcError -4)."""
+        self._check(self._L.mmpc_set_barrier_rule(self._h, int(rule)))
+
+    def barrier_rule(self) -> int:
+        r = C.c_int32(-1)
+        self._check(self._L.mmpc_get_barrier_rule(self._h, C.byref(r)))
+        return int(r.value)
 
     def kkt_solver_for(self, B: int) -> int:
         """KKT_* solver a solve of B instances runs (the AUTO choice resolved)."""
