@@ -73,7 +73,9 @@ enum mmpc_result {
     MMPC_ERR_NO_DEVICE = -6
 };
 
-/* per-instance solver status (status[] outputs) */
+/* per-instance solver status (status[] outputs).  Under state bounds (the interior-point variant) non-finite input
+   data may surface as LINESEARCH_FAILED, NONFINITE or FACTORIZATION_FAILED (2, 3 or 4): which test meets the NaN/Inf
+   first depends on where it enters the barrier terms; the instance's neighbours in the batch are unaffected. */
 enum mmpc_status {
     MMPC_STATUS_CONVERGED = 0,            /* ||grad||_inf <= tol_grad and ||g||_inf <= tol_defect */
     MMPC_STATUS_MAX_ITER = 1,             /* opts.max_iter SQP iterations without convergence */

@@ -10,6 +10,9 @@ active controls held).  The polished point is checked to be a KKT point: equalit
 multipliers of the right sign, inactive bounds satisfied, stationarity |grad + C^T lam| <= 1e-9.
 
 Writes tests/golden/xbounds_golden.json: 4 two-link instances (N = 30) and 1 exo instance (N = 20).
+With the argument `edges` it writes tests/golden/xbounds_edges_golden.json instead and leaves the first file alone:
+6 two-link instances (N = 1, 2, 16, 17) and 2 exo instances (N = 2, 7) with one-sided and single-component state
+bounds, some with one-sided control bounds (EDGE_SPECS).
 """
 from __future__ import annotations
 
@@ -159,5 +162,59 @@ def main():
                        cases=cases), fh, allow_nan=True)
 
 
+# ---- second set: horizon edges and one-sided bounds (tests/test_gpu_bounded_shapes.py's inputs) ----
+W2 = np.array([10.0, 1.0, 5.0, 5.0, 5.0, 5.0, 0.01, 0.01])
+WX = np.array([10.0] * 4 + [1.0] * 4 + [1.0] * 4 + [0.01] * 4)
+INF = np.inf
+EDGE_PATTERNS = {  # name: (x_lb, x_ub, u_lb, u_ub, clip of the measured velocities)
+    "box": ([-INF, -INF, -0.5, -0.5], [INF, INF, 0.5, 0.5], [-INF, -INF], [INF, INF], 0.499),
+    "mixed": ([-INF, -INF, -0.5, -INF], [INF, INF, INF, 0.5], [-INF, -INF], [INF, INF], 0.499),
+    "mixed+u": ([-INF, -INF, -0.5, -INF], [INF, INF, INF, 0.5], [-1.0, -INF], [INF, 1.0], 0.499),
+    "one_sided": ([-INF] * 4 + [-0.2, -INF, -INF, -0.2], [INF] * 4 + [INF, 0.2, INF, INF], [-INF] * 4, [INF] * 4, 0.15),
+}
+# (model, N, pattern, instance of the seed-20250213 stream from index 0).  Chosen among the instances of the GPU sweep
+# whose solutions have active bounds and where the interior-point oracle lands within 2.5e-7 relative of the polished
+# point (a quarter of the 1e-6 the tests allow; instance 0 of N = 16 and N = 17 under mixed+u sits at 6.5e-7: left out)
+EDGE_SPECS = [
+    ("two_link_arm", 1, "box", 0),
+    ("two_link_arm", 2, "mixed", 0),
+    ("two_link_arm", 16, "mixed+u", 3),
+    ("two_link_arm", 16, "mixed+u", 6),
+    ("two_link_arm", 16, "mixed+u", 9),
+    ("two_link_arm", 17, "mixed+u", 4),
+    ("exo_arm", 2, "one_sided", 0),
+    ("exo_arm", 7, "one_sided", 0),
+]
+
+
+def main_edges():
+    """Writes tests/golden/xbounds_edges_golden.json; xbounds_golden.json is not touched."""
+    h = 0.002
+    cases = []
+    for model, N, pat, b in EDGE_SPECS:
+        exo = model == "exo_arm"
+        nx, nu = (8, 4) if exo else (4, 2)
+        xl, xu, ul, uu, clip = EDGE_PATTERNS[pat]
+        xl, xu, ul, uu = map(np.array, (xl, xu, ul, uu))
+        x0, up, tr = (gx.synth_exo if exo else g2.synth_two_link)(20250213, b, 1, N, h)
+        x0[0, nx // 2:] = np.clip(x0[0, nx // 2:], -clip, clip)  # the measured state inside the velocity box
+        w = WX if exo else W2
+        V, J, stat, na, nh = solve(x0[0], up[0], tr[0], w, h, gx.f if exo else g2.f, gx.jac if exo else g2.jac, nx, nu,
+                                   xl, xu, ul, uu)
+        print(model, N, pat, b, J, stat, na, nh, flush=True)
+        cases.append(dict(model=model, N=N, pattern=pat, index=b, x0=x0[0].tolist(), u_prev=up[0].tolist(),
+                          traj=tr[0].tolist(), weights=w.tolist(), x_lb=[float(v) for v in xl],
+                          x_ub=[float(v) for v in xu], u_lb=[float(v) for v in ul], u_ub=[float(v) for v in uu],
+                          V=V.tolist(), J=J, stationarity=stat, n_active_x=na, n_active_u=nh))
+    with open(os.path.join(HERE, "xbounds_edges_golden.json"), "w") as fh:
+        json.dump(dict(h=h, seed=20250213,
+                       solver="scipy SLSQP on the single-shooting form (state bounds as inequality constraints, "
+                              "exact sensitivities), then Gauss-Newton SQP polish on the active set; KKT checked",
+                       cases=cases), fh, allow_nan=True)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["edges"]:
+        main_edges()
+    else:
+        main()

@@ -142,3 +142,44 @@ def test_oracle_state_bounds_exact_vs_gauss_newton_iterations(oracle):
     assert rel.max() < 1e-6
     print("GN", np.bincount(gn["iters"]), gn["iters"].mean(), "EXACT", np.bincount(ex["iters"]), ex["iters"].mean(),
           "fallbacks", oracle.exact_fallbacks(reset=True))
+
+
+@pytest.mark.parametrize("hessian", ["gn", "exact"])
+def test_oracle_state_bounds_edges_match_scipy(hessian, oracle):
+    """tests/golden/xbounds_edges_golden.json: one-sided and single-component state bounds, with and without one-sided
+    control bounds, at N = 1, 2, 7, 16, 17 (the inputs of tests/test_gpu_bounded_shapes.py).  The interior-point oracle
+    under both Hessians reaches each scipy KKT point: V* within 1e-6 relative, the same active state bounds and the
+    same controls on a bound, every state inside its box."""
+    gold = load_golden("xbounds_edges_golden.json")
+    h = gold["h"]
+    hess = oracle.HESS_EXACT if hessian == "exact" else oracle.HESS_GAUSS_NEWTON
+    assert len(gold["cases"]) == 8
+    for case in gold["cases"]:
+        model = oracle.EXO if case["model"] == "exo_arm" else oracle.TWO_LINK
+        nx, nu = oracle.DIMS[model]
+        N = case["N"]
+        xl, xu = np.array(case["x_lb"]), np.array(case["x_ub"])
+        ul, uu = np.array(case["u_lb"]), np.array(case["u_ub"])
+        r = oracle.solve_batch(N, h, np.array(case["x0"])[None], np.array(case["u_prev"])[None],
+                               np.array(case["traj"])[None], np.array(case["weights"]), u_lb=ul, u_ub=uu, x_lb=xl,
+                               x_ub=xu, max_iter=200, model=model, hessian=hess)
+        tag = (case["model"], N, case["pattern"], case["index"])
+        assert r["status"][0] == 0, (tag, r["status"], r["iters"])
+        V, Vg = r["V"][0], np.array(case["V"])
+        rel = np.abs(V - Vg).max() / np.abs(Vg).max()
+        print(tag, hessian, r["iters"][0], "iterations, V*", rel, "from scipy")
+        assert rel < 1e-6, (tag, rel)
+        # the recipe's selection rule (EDGE_SPECS): a quarter of the tolerance is left to the kernels' other rounding
+        assert rel <= 2.5e-7, (tag, rel)
+        assert abs(r["J"][0] - case["J"]) / case["J"] < 1e-8
+        X, Xg = states(V, N, nx, nu), states(Vg, N, nx, nu)
+        assert (X >= xl - 1e-12).all() and (X <= xu + 1e-12).all()
+        act_g = (np.abs(Xg - xl) < 1e-9) | (np.abs(Xg - xu) < 1e-9)
+        act = (np.abs(X - xl) < 1e-6) | (np.abs(X - xu) < 1e-6)
+        assert act_g.sum() == case["n_active_x"] and (act == act_g).all(), tag
+        U = np.array([V[k * (nx + nu) + nx:(k + 1) * (nx + nu)] for k in range(N)])
+        Ug = np.array([Vg[k * (nx + nu) + nx:(k + 1) * (nx + nu)] for k in range(N)])
+        assert (U >= ul).all() and (U <= uu).all()
+        held_g = (np.abs(Ug - ul) < 1e-9) | (np.abs(Ug - uu) < 1e-9)
+        held = (np.abs(U - ul) < 1e-6) | (np.abs(U - uu) < 1e-6)
+        assert held_g.sum() == case["n_active_u"] and (held == held_g).all(), tag
