@@ -266,6 +266,39 @@ int mmpc_solve_batch_host(mmpc_handle* h, int64_t B, const double* x0, const dou
                           const double* u_lb, const double* u_ub, double* V_inout, int32_t* status,
                           int32_t* iters, double* kkt_res);
 
+/* ---- per-instance control bounds (additive to ABI 6, as mmpc_set_barrier_rule was) ----
+ * The reference's control limits belong to one controller: ModelControl::update_control_limits
+ * (ModelControl.cpp:205-209) replaces that controller's u_min / u_max at run time and calc_u writes them into its own
+ * lbx / ubx every tick (:147-157).  The *_bounds entry points carry B such limit sets through one launch: each is the
+ * entry point above of the same name plus `bounds_stride` after u_ub, and the entry points above forward to them with
+ * bounds_stride 0.
+ *   bounds_stride == 0    u_lb / u_ub are [nu], shared by the batch (the meaning above).
+ *   bounds_stride >= nu   instance b's row starts at b * bounds_stride in both arrays (one stride serves both); a
+ *                         buffer of (B - 1) bounds_stride + nu doubles is enough and is never read past that (the
+ *                         rule of the RCCL path's per-instance weights); columns nu .. bounds_stride - 1 are padding
+ *                         that no kernel or scan reads.
+ *   any other value       MMPC_ERR_INVALID_ARG, mmpc_last_error names `bounds_stride`; checked before any device call
+ *                         (and, in the RCCL entry, before anything is sent).  The kernels take the stride as 32
+ *                         bits: above 2^31 - 1 it is MMPC_ERR_UNSUPPORTED.
+ * Shared-bounds solves run the kernels they ran before, unchanged; bounds_stride != 0 selects per-instance variants of
+ * the bounded Riccati kernels (compiled separately: as per-lane values the bounds cost the shared-bounds solves
+ * 3-10 %), the condensed kernel reads its row through a run-time stride.
+ * Either pointer may be NULL as above (the RCCL entry keeps its "both or neither" rule).  |b| >= 1e19 is infinite per
+ * element; an instance whose row is all infinite is solved by the bounded kernel with infinite bounds -- the kernel
+ * is chosen per batch from the pointers, as above.  The host entries keep their "all infinite -> unbounded kernels"
+ * rule over all B rows (a multi-device solve: over each shard's rows).  Every kernel reads the row of the INSTANCE,
+ * also in the lane solver's resume launch (the hand-over list's slots are not instances).  State bounds stay per
+ * handle. */
+int mmpc_solve_batch_bounds(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                            const double* traj, const double* weights, int64_t weights_stride,
+                            const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                            int32_t* status, int32_t* iters, double* kkt_res, double* u0_out, void* stream);
+/* HOST pointers, synchronous; stages (B - 1) bounds_stride + nu doubles per array when the bounds are strided */
+int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                                 const double* traj, const double* weights, int64_t weights_stride,
+                                 const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                 int32_t* status, int32_t* iters, double* kkt_res);
+
 /* Continuous-time linearisation at (x[b], u[b]): A = df/dx [nx*nx], B = df/du [nx*nu]
  * column-major, xdot = f(x,u) [nx].  DEVICE pointers; any output may be NULL. */
 int mmpc_linearize_batch(mmpc_handle* h, int64_t B, const double* x, const double* u,
@@ -342,6 +375,18 @@ int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, cons
                                 const double* traj, const double* weights, int64_t weights_stride,
                                 const double* u_lb, const double* u_ub, double* V_inout, int32_t* status,
                                 int32_t* iters, double* kkt_res, void* stream);
+/* The two multi-device solves with per-instance control bounds (bounds_stride: see mmpc_solve_batch_bounds).  The host
+ * entry gives shard g the rows from first * bounds_stride on.  The RCCL entry sends each shard's rows by
+ * ncclSend/ncclRecv (the last row up to its nu entries, so (B - 1) bounds_stride + nu doubles are never over-read), as
+ * it does for per-instance weights, and keeps ncclBroadcast for bounds_stride 0. */
+int mmpc_multi_solve_batch_host_bounds(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                       int32_t* status, int32_t* iters, double* kkt_res);
+int mmpc_multi_solve_batch_rccl_bounds(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                       int32_t* status, int32_t* iters, double* kkt_res, void* stream);
 /* the version of the RCCL library the call above loads (ncclGetVersion, e.g. 22606), MMPC_ERR_UNSUPPORTED if none */
 int mmpc_rccl_version(int32_t* version);
 

@@ -28,6 +28,18 @@ hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const S
     return hipGetLastError();
 }
 #ifdef MMPC_GROUP_BOUNDED_UNIT
+// per-instance control bounds (SolveParams::b_stride != 0): the bounded variants once more, sqp_group_instb_kernel
+template <bool BOUNDED, bool XB, bool EXACT, bool MEHR>
+hipError_t launch_instb(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
+    auto* k = sqp_group_instb_kernel<TwoLinkArm, BOUNDED, XB, EXACT, MEHR>;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    k<<<grid, block, lds, stream>>>(p, gwk);
+    return hipGetLastError();
+}
 // the interior point under Mehrotra's predictor-corrector rule (mmpc_set_barrier_rule)
 template <bool EXACT>
 hipError_t launch_mehrotra(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
@@ -57,6 +69,12 @@ hipError_t group_two_link_phase_cycles(unsigned long long* out16, int n, bool re
 #else
 hipError_t launch_group_two_link_bounded(bool xb, bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                                          const SolveParams& p, const GroupWork& gwk) {
+    if (p.b_stride != 0) {
+        if (xb) return exact ? launch_instb<false, true, true, false>(grid, block, lds, stream, p, gwk)
+                             : launch_instb<false, true, false, false>(grid, block, lds, stream, p, gwk);
+        return exact ? launch_instb<true, false, true, false>(grid, block, lds, stream, p, gwk)
+                     : launch_instb<true, false, false, false>(grid, block, lds, stream, p, gwk);
+    }
     if (xb) return exact ? launch<false, true, true>(grid, block, lds, stream, p, gwk)   // the interior point
                          : launch<false, true>(grid, block, lds, stream, p, gwk);
     return exact ? launch<true, false, true>(grid, block, lds, stream, p, gwk)
@@ -64,6 +82,9 @@ hipError_t launch_group_two_link_bounded(bool xb, bool exact, dim3 grid, dim3 bl
 }
 hipError_t launch_group_two_link_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                                           const SolveParams& p, const GroupWork& gwk) {
+    if (p.b_stride != 0)
+        return exact ? launch_instb<false, true, true, true>(grid, block, lds, stream, p, gwk)
+                     : launch_instb<false, true, false, true>(grid, block, lds, stream, p, gwk);
     return exact ? launch_mehrotra<true>(grid, block, lds, stream, p, gwk)
                  : launch_mehrotra<false>(grid, block, lds, stream, p, gwk);
 }

@@ -21,6 +21,18 @@ namespace {
 template <class Model, class FT>
 void launch_lane(bool bounded, bool xb, bool exact, dim3 grid, dim3 block, hipStream_t stream, const SolveParams& p,
                  LaneWork lw) {
+    if (p.b_stride != 0 && (xb || bounded)) {   // per-instance control bounds: the IB instantiations
+        if constexpr (HasHess<Model>::value && std::is_same<FT, double>::value) {
+            if (exact) {
+                if (xb) sqp_lane_kernel<Model, double, false, true, true, true><<<grid, block, 0, stream>>>(p, lw);
+                else sqp_lane_kernel<Model, double, true, false, true, true><<<grid, block, 0, stream>>>(p, lw);
+                return;
+            }
+        }
+        if (xb) sqp_lane_kernel<Model, FT, false, true, false, true><<<grid, block, 0, stream>>>(p, lw);
+        else sqp_lane_kernel<Model, FT, true, false, false, true><<<grid, block, 0, stream>>>(p, lw);
+        return;
+    }
     if constexpr (HasHess<Model>::value && std::is_same<FT, double>::value) {
         if (exact) {
             if (xb) sqp_lane_kernel<Model, double, false, true, true><<<grid, block, 0, stream>>>(p, lw);

@@ -750,6 +750,14 @@ int launch_group(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const So
     sqp_group_kernel<Model, BOUNDED, XB, EXACT><<<grid, block, lds, stream>>>(p, gwk);
     return MMPC_OK;
 }
+// the bounded 16-lane kernels with per-instance control bounds (SolveParams::b_stride != 0)
+template <class Model, bool BOUNDED, bool XB, bool EXACT, bool MEHR>
+int launch_group_instb(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
+    int rc = set_dynamic_lds(sqp_group_instb_kernel<Model, BOUNDED, XB, EXACT, MEHR>, lds);
+    if (rc) return rc;
+    sqp_group_instb_kernel<Model, BOUNDED, XB, EXACT, MEHR><<<grid, block, lds, stream>>>(p, gwk);
+    return MMPC_OK;
+}
 // the 16-lane kernel of model M for (ub: control bounds only, xb: state bounds, exact Hessian); `what` names the launch
 // in an error text.  The built-in 2-link arm's kernels live in the units of group_launch.h.
 template <class M>
@@ -760,6 +768,15 @@ int dispatch_group(bool ub, bool xb, bool exact, dim3 grid, dim3 block, size_t l
                                         : launch_group_two_link(exact, grid, block, lds, stream, p, gwk);
         return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     } else {
+        if (p.b_stride != 0 && (ub || xb)) {   // per-instance control bounds
+            if constexpr (exact_capable<M>()) {
+                if (exact)
+                    return xb ? launch_group_instb<M, false, true, true, false>(grid, block, lds, stream, p, gwk)
+                              : launch_group_instb<M, true, false, true, false>(grid, block, lds, stream, p, gwk);
+            }
+            return xb ? launch_group_instb<M, false, true, false, false>(grid, block, lds, stream, p, gwk)
+                      : launch_group_instb<M, true, false, false, false>(grid, block, lds, stream, p, gwk);
+        }
         if constexpr (exact_capable<M>()) {
             if (exact)
                 return xb   ? launch_group<M, false, true, true>(grid, block, lds, stream, p, gwk)
@@ -781,6 +798,12 @@ int dispatch_group_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipSt
         const hipError_t e = launch_group_two_link_mehrotra(exact, grid, block, lds, stream, p, gwk);
         return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string("group kernel launch: ") + hipGetErrorString(e));
     } else if constexpr (M::NX + M::NU < kGroupLanes) {
+        if (p.b_stride != 0) {   // per-instance control bounds
+            if constexpr (exact_capable<M>()) {
+                if (exact) return launch_group_instb<M, false, true, true, true>(grid, block, lds, stream, p, gwk);
+            }
+            return launch_group_instb<M, false, true, false, true>(grid, block, lds, stream, p, gwk);
+        }
         if constexpr (exact_capable<M>()) {
             if (exact) {
                 const int rc = set_dynamic_lds(sqp_group_mehrotra_kernel<M, true>, lds);
@@ -898,16 +921,28 @@ int query_cu_count(mmpc_handle* h) {
     return MMPC_OK;
 }
 
+// u_lb / u_ub rows of the *_bounds entry points: 0 = one shared [nu] row, >= nu = a row per instance.  Pure
+// arithmetic: every entry point checks it before its first device call.
+int check_bounds_stride(const mmpc_model_info& mi, int64_t b_stride) {
+    if (b_stride != 0 && b_stride < mi.num_u)
+        return fail(MMPC_ERR_INVALID_ARG, "bounds_stride must be 0 (shared) or >= nu (" + std::to_string(mi.num_u) +
+                                              "), got " + std::to_string(b_stride));
+    if (b_stride > 0x7fffffffLL)   // the kernels take it as 32 bits (SolveParams::b_stride)
+        return fail(MMPC_ERR_UNSUPPORTED, "bounds_stride above 2^31 - 1 is not supported");
+    return MMPC_OK;
+}
+
 int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
                  const double* weights, int64_t w_stride, const double* u_lb, const double* u_ub, double* V,
                  int32_t* status, int32_t* iters, double* kkt, hipStream_t stream, double* trace = nullptr,
-                 double* u0_out = nullptr) {
+                 double* u0_out = nullptr, int64_t b_stride = 0) {
     const mmpc_model_info& mi = h->info;
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
     if (B == 0) return MMPC_OK;
     if (!x0 || !u_prev || !traj || !weights || !V) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     const int nw = mi.num_x + 2 * mi.num_u;
     if (w_stride != 0 && w_stride < nw) return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
+    if (int rc = check_bounds_stride(mi, b_stride)) return rc;
     if (B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
     SolveParams p;
     p.B = B;
@@ -924,6 +959,7 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     p.w_stride = w_stride;
     p.u_lb = u_lb;
     p.u_ub = u_ub;
+    p.b_stride = static_cast<int32_t>(b_stride);
     p.V = V;
     p.status = status;
     p.iters = iters;
@@ -1286,8 +1322,17 @@ int mmpc_solve_batch_u0(mmpc_handle* h, int64_t B, const double* x0, const doubl
                         const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                         double* V_inout, int32_t* status, int32_t* iters, double* kkt_res, double* u0_out,
                         void* stream) {
+    return mmpc_solve_batch_bounds(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, 0, V_inout, status,
+                                   iters, kkt_res, u0_out, stream);
+}
+
+int mmpc_solve_batch_bounds(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
+                            const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                            int64_t bounds_stride, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res,
+                            double* u0_out, void* stream) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;   // before any device call
     if (B == 0) return MMPC_OK;
     if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     int dev;
@@ -1296,7 +1341,7 @@ int mmpc_solve_batch_u0(mmpc_handle* h, int64_t B, const double* x0, const doubl
     DeviceGuard g(dev);
     if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
     return launch_solve(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, V_inout, status, iters,
-                        kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out);
+                        kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out, bounds_stride);
 }
 
 int mmpc_host_alloc(uint64_t bytes, void** out) {
@@ -1320,25 +1365,39 @@ int mmpc_host_free(void* p) {
 int mmpc_solve_batch_host(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
                           const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                           double* V_inout, int32_t* status, int32_t* iters, double* kkt_res) {
+    return mmpc_solve_batch_host_bounds(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, 0, V_inout,
+                                        status, iters, kkt_res);
+}
+
+int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                                 const double* traj, const double* weights, int64_t weights_stride,
+                                 const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                 int32_t* status, int32_t* iters, double* kkt_res) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;   // before the rows are scanned
     if (B == 0) return MMPC_OK;
     if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     std::lock_guard<std::mutex> lk(h->host_mu);
     const mmpc_model_info& mi = h->info;
     const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
-    // bounds that are all infinite (|b| >= 1e19, the reference's +-1e31 defaults) select the unbounded kernels
+    // bounds that are all infinite (|b| >= 1e19, the reference's +-1e31 defaults) select the unbounded kernels:
+    // every row of per-instance bounds is scanned, its nu entries only (not the padding of a wider stride)
+    const size_t bst = static_cast<size_t>(bounds_stride), brows = bst ? static_cast<size_t>(B) : 1;
     bool lb_finite = false, ub_finite = false;
-    for (size_t c = 0; c < nu; ++c) {
-        lb_finite |= u_lb && u_lb[c] > -1e19;
-        ub_finite |= u_ub && u_ub[c] < 1e19;
-    }
+    for (size_t b = 0; b < brows; ++b)
+        for (size_t c = 0; c < nu; ++c) {
+            lb_finite |= u_lb && u_lb[b * bst + c] > -1e19;
+            ub_finite |= u_ub && u_ub[b * bst + c] < 1e19;
+        }
     if (!lb_finite && !ub_finite) u_lb = u_ub = nullptr;
     const size_t nw = nx + 2 * nu;
     const size_t nW = weights_stride ? (size_t)B * (size_t)weights_stride : nw;
+    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
+    const size_t nB = (brows - 1) * bst + nu;
     // doubles: x0, u_prev, traj, weights, lb, ub, V, kkt ; ints: status, iters (as doubles' room)
     const size_t off_x0 = 0, off_up = off_x0 + B * nx, off_tr = off_up + B * nu, off_w = off_tr + B * N * nx;
-    const size_t off_lb = off_w + nW, off_ub = off_lb + nu, off_V = off_ub + nu, off_kkt = off_V + B * NV;
+    const size_t off_lb = off_w + nW, off_ub = off_lb + nB, off_V = off_ub + nB, off_kkt = off_V + B * NV;
     const size_t off_st = off_kkt + B, off_it = off_st + (B + 1) / 2, total = off_it + (B + 1) / 2;
     int dev;
     int rc = resolve_device(h, &dev);
@@ -1353,13 +1412,14 @@ int mmpc_solve_batch_host(mmpc_handle* h, int64_t B, const double* x0, const dou
     MMPC_HIP(hipMemcpyAsync(d + off_up, u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
     MMPC_HIP(hipMemcpyAsync(d + off_tr, traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
     MMPC_HIP(hipMemcpyAsync(d + off_w, weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nu * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nu * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
     MMPC_HIP(hipMemcpyAsync(d + off_V, V_inout, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
     int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
     int32_t* dit = reinterpret_cast<int32_t*>(d + off_it);
     rc = launch_solve(h, B, d + off_x0, d + off_up, d + off_tr, d + off_w, weights_stride, u_lb ? d + off_lb : nullptr,
-                      u_ub ? d + off_ub : nullptr, d + off_V, dst, dit, d + off_kkt, s);
+                      u_ub ? d + off_ub : nullptr, d + off_V, dst, dit, d + off_kkt, s, nullptr, nullptr,
+                      bounds_stride);
     if (rc) return rc;
     MMPC_HIP(hipMemcpyAsync(V_inout, d + off_V, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
     if (status) MMPC_HIP(hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1665,8 +1725,17 @@ int mmpc_multi_handle(mmpc_multi* m, int32_t g, mmpc_handle** h) {
 int mmpc_multi_solve_batch_host(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev, const double* traj,
                                 const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                                 double* V_inout, int32_t* status, int32_t* iters, double* kkt_res) {
+    return mmpc_multi_solve_batch_host_bounds(m, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, 0, V_inout,
+                                              status, iters, kkt_res);
+}
+
+int mmpc_multi_solve_batch_host_bounds(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                       int32_t* status, int32_t* iters, double* kkt_res) {
     if (!m) return fail(MMPC_ERR_INVALID_ARG, "null multi-device handle");
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(m->h[0]->info, bounds_stride)) return rc;   // before any shard starts
     if (B == 0) return MMPC_OK;
     if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     std::lock_guard<std::mutex> lk(m->mu);
@@ -1681,9 +1750,11 @@ int mmpc_multi_solve_batch_host(mmpc_multi* m, int64_t B, const double* x0, cons
         int64_t first = 0, count = 0;
         mmpc_shard(B, G, g, &first, &count);
         if (count == 0) return;
-        const int rc = mmpc_solve_batch_host(
+        // per-instance bounds: the shard's rows start at first * bounds_stride (stride 0: the shared row)
+        const int rc = mmpc_solve_batch_host_bounds(
             m->h[static_cast<size_t>(g)], count, x0 + first * nx, u_prev + first * nu, traj + first * N * nx,
-            weights_stride ? weights + first * weights_stride : weights, weights_stride, u_lb, u_ub,
+            weights_stride ? weights + first * weights_stride : weights, weights_stride,
+            u_lb ? u_lb + first * bounds_stride : nullptr, u_ub ? u_ub + first * bounds_stride : nullptr, bounds_stride,
             V_inout + first * NV, status ? status + first : nullptr, iters ? iters + first : nullptr,
             kkt_res ? kkt_res + first : nullptr);
         rcs[static_cast<size_t>(g)] = rc;
@@ -1718,8 +1789,18 @@ int mmpc_rccl_version(int32_t* version) {
 int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev, const double* traj,
                                 const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                                 double* V_inout, int32_t* status, int32_t* iters, double* kkt_res, void* stream) {
+    return mmpc_multi_solve_batch_rccl_bounds(m, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, 0, V_inout,
+                                              status, iters, kkt_res, stream);
+}
+
+int mmpc_multi_solve_batch_rccl_bounds(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
+                                       int32_t* status, int32_t* iters, double* kkt_res, void* stream) {
     if (!m) return fail(MMPC_ERR_INVALID_ARG, "null multi-device handle");
     if (B < 0 || weights_stride < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0 or weights_stride < 0");
+    // checked before anything is sent: the scatter reads rows of bounds_stride
+    if (int rc = check_bounds_stride(m->h[0]->info, bounds_stride)) return rc;
     if (B == 0) return MMPC_OK;
     if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     if ((u_lb == nullptr) != (u_ub == nullptr)) return fail(MMPC_ERR_INVALID_ARG, "u_lb and u_ub go together");
@@ -1762,11 +1843,14 @@ int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, cons
         int32_t *st, *it;
     };
     std::vector<Shard> sh(static_cast<size_t>(G));
+    // bound doubles of a shard of c instances: the shared row, or c rows of which the last ends after its nu entries
+    const int64_t bst = bounds_stride;
+    auto nbs = [&](int64_t c) { return bst ? (c > 0 ? (c - 1) * bst + nu : 0) : nu; };
     for (int32_t g = 0; g < G; ++g) {   // shard buffers on device g (grown only)
         Shard& s = sh[static_cast<size_t>(g)];
         mmpc_shard(B, G, g, &s.first, &s.count);
         const int64_t c = s.count;
-        const int64_t nd = c * (nx + nu + N * nx + NV + 1) + (shared_w ? nw : c * wst) + 2 * nu;
+        const int64_t nd = c * (nx + nu + N * nx + NV + 1) + (shared_w ? nw : c * wst) + 2 * nbs(c);
         const size_t bytes = static_cast<size_t>(nd) * sizeof(double) + static_cast<size_t>(2 * c) * sizeof(int32_t) + 64;
         DeviceGuard dg(m->dev[g]);
         if (bytes > m->buf_bytes[g]) {
@@ -1783,8 +1867,8 @@ int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, cons
         s.V = p; p += c * NV;
         s.kkt = p; p += c;
         s.w = p; p += shared_w ? nw : c * wst;
-        s.lb = p; p += nu;
-        s.ub = p; p += nu;
+        s.lb = p; p += nbs(c);
+        s.ub = p; p += nbs(c);
         s.st = reinterpret_cast<int32_t*>(p);
         s.it = s.st + c;
     }
@@ -1846,10 +1930,17 @@ int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, cons
                 op(R->send(weights + s.first * wst, nwc, f64, g, c0, s0), "ncclSend weights", g);
                 op(R->recv(s.w, nwc, f64, 0, cg, sg), "ncclRecv weights", g);
             }
+            if (u_lb && bst) {   // per-instance bounds: the shard's rows, the last one up to its nu entries
+                const size_t nbc = static_cast<size_t>(nbs(s.count));
+                op(R->send(u_lb + s.first * bst, nbc, f64, g, c0, s0), "ncclSend u_lb", g);
+                op(R->recv(s.lb, nbc, f64, 0, cg, sg), "ncclRecv u_lb", g);
+                op(R->send(u_ub + s.first * bst, nbc, f64, g, c0, s0), "ncclSend u_ub", g);
+                op(R->recv(s.ub, nbc, f64, 0, cg, sg), "ncclRecv u_ub", g);
+            }
         }
         // collectives run on every rank, shards of count 0 included (the broadcast lands in its unused buffer)
         if (shared_w) op(R->broadcast(weights, s.w, static_cast<size_t>(nw), f64, 0, cg, sg), "ncclBroadcast weights", g);
-        if (u_lb) {
+        if (u_lb && !bst) {
             op(R->broadcast(u_lb, s.lb, static_cast<size_t>(nu), f64, 0, cg, sg), "ncclBroadcast u_lb", g);
             op(R->broadcast(u_ub, s.ub, static_cast<size_t>(nu), f64, 0, cg, sg), "ncclBroadcast u_ub", g);
         }
@@ -1860,9 +1951,9 @@ int mmpc_multi_solve_batch_rccl(mmpc_multi* m, int64_t B, const double* x0, cons
     for (int32_t g = 0; g < G; ++g) {
         const Shard& s = sh[static_cast<size_t>(g)];
         if (s.count == 0) continue;
-        const int rc = mmpc_solve_batch(m->h[static_cast<size_t>(g)], s.count, s.x0, s.up, s.tr, s.w, wst,
-                                        u_lb ? s.lb : nullptr, u_lb ? s.ub : nullptr, s.V, s.st, s.it, s.kkt,
-                                        m->st[static_cast<size_t>(g)]);
+        const int rc = mmpc_solve_batch_bounds(m->h[static_cast<size_t>(g)], s.count, s.x0, s.up, s.tr, s.w, wst,
+                                               u_lb ? s.lb : nullptr, u_lb ? s.ub : nullptr, bst, s.V, s.st, s.it,
+                                               s.kkt, nullptr, m->st[static_cast<size_t>(g)]);
         if (rc) {
             const std::string err = "device " + std::to_string(m->dev[static_cast<size_t>(g)]) + ": " + g_last_error;
             return drain(fail(rc, err));

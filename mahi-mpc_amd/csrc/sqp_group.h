@@ -222,6 +222,7 @@ __device__ __forceinline__ void group_model(bool lin, const double* lFq, const d
 template <class Model, bool BOUNDED = false, bool XB = false, bool EXACT = false>
 __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork gw) {
     constexpr bool MEHR = false;
+    constexpr bool IB = false;   // shared control bounds; per-instance rows: sqp_group_instb_kernel (end of the file)
 #endif  // MMPC_GROUP_PASS == 1
 #if MMPC_GROUP_PASS != 0   // ---- the kernel body: Model, BOUNDED, XB, EXACT, MEHR, p, gw in scope ----
     static_assert(!(BOUNDED && XB), "the interior-point variant handles the control bounds itself");
@@ -314,7 +315,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         up[c] = p.u_prev[ii * NU + c];
     }
     double lbv[NU], ubv[NU];
-    load_bounds<NU, BOUNDED>(p, lbv, ubv);
+    load_bounds<NU, BOUNDED, IB>(p, inst, lbv, ubv);
     // ---- lane-distributed Riccati (DIST): lane r of the group owns row r of the augmented value function
     //      P~ (NS x NS) and of every per-row quantity; small per-stage quantities are computed redundantly on
     //      all lanes; rows are exchanged with row_bcast.  Control bounds (BOUNDED) run the same
@@ -399,7 +400,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     double yl[XB ? NY : 1], yu[XB ? NY : 1];
     double mub = (XB && resume) ? p.tail_mub[slot] : kIpMu0;  // barrier parameter (f = J/2 scale)
     if constexpr (XB) {
-        load_ip_bounds<NX, NU>(p, yl, yu);
+        load_ip_bounds<NX, NU, IB>(p, inst, yl, yu);
         __builtin_amdgcn_wave_barrier();
         if (resume) {   // the handed-over duals, from the lane launch's workspace (the iterate is interior already)
             const double* const lz = p.tail_lws + (inst >> 6) * p.tail_lws_block + (inst & 63);
@@ -2166,6 +2167,20 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
 template <class Model, bool EXACT = false>
 __global__ __launch_bounds__(64) void sqp_group_mehrotra_kernel(SolveParams p, GroupWork gw) {
     constexpr bool BOUNDED = false, XB = true, MEHR = true;
+    constexpr bool IB = false;
+#define MMPC_GROUP_BODY_ONLY
+#include "sqp_group.h"
+#undef MMPC_GROUP_BODY_ONLY
+}
+
+// The bounded variants with PER-INSTANCE control bounds (mmpc_solve_batch_bounds, bounds_stride >= nu): the body once
+// more with IB = true, where load_bounds / load_ip_bounds read row `inst` of u_lb / u_ub -- the instance, never the
+// launch slot of a resume launch.  A kernel of its own and not a run-time stride in the kernels above: their bounds
+// are wave-uniform scalar loads, and as per-lane values they cost the shared-bounds solves 3-10 %.
+template <class Model, bool BOUNDED, bool XB, bool EXACT = false, bool MEHR = false>
+__global__ __launch_bounds__(64) void sqp_group_instb_kernel(SolveParams p, GroupWork gw) {
+    static_assert(BOUNDED || XB, "per-instance bounds: the bounded variants only");
+    constexpr bool IB = true;
 #define MMPC_GROUP_BODY_ONLY
 #include "sqp_group.h"
 #undef MMPC_GROUP_BODY_ONLY

@@ -186,13 +186,17 @@ __device__ __forceinline__ gmem<double>* stage_ptr(double* wsb, int64_t k, int S
 // the Gauss-Newton ones (the hold rule acts on H_ww, H_wx, h_w after W is added).  With state bounds (XB, round 6:
 // IPOPT's exact Hessian under the barrier) W_k joins the barrier-augmented stage blocks (Sigma, b) -- the adjoint
 // that weights it carries the bound duals -- and a sweep whose H_ww is not positive definite is redone without W.
-template <class Model, class FT = double, bool BOUNDED = false, bool XB = false, bool EXACT = false>
+// IB: per-instance control bounds (mmpc_solve_batch_bounds, bounds_stride >= nu) -- row `inst` of u_lb / u_ub.  A
+// compile-time flag, defaulted: the shared-bounds instantiations keep their code (as per-lane values the bounds cost the
+// exo's control-bounded solves 10 %); only BOUNDED and XB kernels are instantiated with it.
+template <class Model, class FT = double, bool BOUNDED = false, bool XB = false, bool EXACT = false, bool IB = false>
 // one wave per SIMD by design (P~ in LDS, ~40 KB per wave): telling the scheduler so lets it schedule for latency
 // rather than for a second wave's registers (cfg#3: 12.06 -> 11.94 ms).  The fp32-factor variant's P~ takes 20 KB, so
 // 8 waves would fit a CU's LDS, but it too runs one wave per SIMD: two (256 registers each) measured slower
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 sqp_lane_kernel(SolveParams p, LaneWork lw) {
     static_assert(!(BOUNDED && XB), "the interior-point variant handles the control bounds itself");
+    static_assert(!IB || BOUNDED || XB, "per-instance bounds: the bounded variants only");
     static_assert(!EXACT || (HasHess<Model>::value && std::is_same<FT, double>::value),
                   "exact Hessian: fp64 solves of models with second derivatives");
     constexpr int NX = Model::NX, NU = Model::NU, NQ = Model::NQ, NA = NX - NQ, NS = NX + NU, ND = NX + NU;
@@ -241,7 +245,7 @@ sqp_lane_kernel(SolveParams p, LaneWork lw) {
         up[c] = p.u_prev[inst * NU + c];
     }
     double lbv[NU], ubv[NU];
-    load_bounds<NU, BOUNDED>(p, lbv, ubv);
+    load_bounds<NU, BOUNDED, IB>(p, inst, lbv, ubv);
     // ---- load: V (reference layout) -> SoA X/U, x_0 pinned (ModelControl.cpp:144-145), targets ----
     // Every copy below loads LB stages into registers before storing them: the workspace stores may alias the input
     // pointers, so a load-store-load order would wait out one memory round trip per element (the load and
@@ -301,7 +305,7 @@ sqp_lane_kernel(SolveParams p, LaneWork lw) {
     double yl[XB ? NY : 1], yu[XB ? NY : 1];
     double mub = kIpMu0;  // barrier parameter (f = J/2 scale)
     if constexpr (XB) {  // y pushed into the interior, z = 1 on finite bounds (oracle solve_one_ip)
-        load_ip_bounds<NX, NU>(p, yl, yu);
+        load_ip_bounds<NX, NU, IB>(p, inst, yl, yu);
         for (int k = 0; k < N; ++k) {
 #pragma unroll
             for (int j = 0; j < NY; ++j) {

@@ -81,7 +81,13 @@ struct SolveParams {
     int tail_lws_ss;         // doubles per stage (x 64 lanes)
     int tail_lws_zl;         // field offset of z_l; z_u follows at + nx + nu
     int gpw;               // 16-lane kernel: instance groups per wave of this launch (kGroupsPerWave, or fewer)
+    // u_lb / u_ub rows: 0 = one [nu] row shared by the batch, >= nu = instance b's row starts at b * b_stride.
+    // Last member, in what was the struct's tail padding: neither the offsets above nor the kernel arguments after
+    // the struct (the workspace pointer) move, so the kernels that never read it keep their code byte for byte.
+    // Read only by the per-instance kernels (IB: sqp_group_instb_kernel, sqp_lane_instb_kernel) and the condensed one.
+    int32_t b_stride;
 };
+static_assert(sizeof(SolveParams) == 520, "b_stride lives in the tail padding: the kernarg layout is unchanged");
 // instance status while handed over (never returned: the resume launch overwrites it)
 constexpr int ST_HANDED_OVER = 6;
 
@@ -118,16 +124,36 @@ __device__ __forceinline__ bool first_iter_filter_accepts(double J0, double c0, 
     if (c0 <= 1e-4 * fmax(1.0, c0) && dJ < 0.0 && alpha * pow(-dJ, 2.3) > pow(c0, 1.1)) return false;
     return ct <= (1.0 - 1e-5) * c0 || Jt <= J0 - 1e-5 * c0;
 }
-// bound values of |b| >= 1e19 are infinite (IPOPT's convention); NaN marks a free control in hold fields
-template <int NU, bool BOUNDED>
-__device__ __forceinline__ void load_bounds(const SolveParams& p, double* lbv, double* ubv) {
+// bound values of |b| >= 1e19 are infinite (IPOPT's convention); NaN marks a free control in hold fields.
+// inst: the INSTANCE (never the launch slot of a resume launch) of a lane or group inside the batch -- the row of
+// per-instance bounds is p.u_lb + inst * p.b_stride (b_stride 0: the one shared row)
+// IB (per-instance bounds): a compile-time variant, because bounds that are wave-uniform scalar loads under shared
+// bounds become 2 nu per-lane registers in kernels that already spill (measured: DESIGN.md 3b "per-instance bounds").
+// !IB is the shared-bounds code unchanged; the condensed kernel, whose row address is wave-uniform either way, always
+// takes IB.
+template <int NU, bool BOUNDED, bool IB = false>
+__device__ __forceinline__ void load_bounds(const SolveParams& p, int64_t inst, double* lbv, double* ubv) {
+    if constexpr (IB) {
+        const double* const lo = (BOUNDED && p.u_lb) ? p.u_lb + inst * (int64_t)p.b_stride : nullptr;
+        const double* const hi = (BOUNDED && p.u_ub) ? p.u_ub + inst * (int64_t)p.b_stride : nullptr;
 #pragma unroll
-    for (int c = 0; c < NU; ++c) {
-        lbv[c] = -INFINITY;
-        ubv[c] = INFINITY;
-        if (BOUNDED) {
-            if (p.u_lb && p.u_lb[c] > -1e19) lbv[c] = p.u_lb[c];
-            if (p.u_ub && p.u_ub[c] < 1e19) ubv[c] = p.u_ub[c];
+        for (int c = 0; c < NU; ++c) {
+            lbv[c] = -INFINITY;
+            ubv[c] = INFINITY;
+            if (BOUNDED) {
+                if (lo && lo[c] > -1e19) lbv[c] = lo[c];
+                if (hi && hi[c] < 1e19) ubv[c] = hi[c];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) {
+            lbv[c] = -INFINITY;
+            ubv[c] = INFINITY;
+            if (BOUNDED) {
+                if (p.u_lb && p.u_lb[c] > -1e19) lbv[c] = p.u_lb[c];
+                if (p.u_ub && p.u_ub[c] < 1e19) ubv[c] = p.u_ub[c];
+            }
         }
     }
 }
@@ -153,12 +179,15 @@ __device__ __forceinline__ double ip_push(double y, double l, double u) {
     return y;
 }
 // bounds of y = (x_{k+1} [nx] | u_k [nu]) of a stage: |b| >= 1e19 is infinite
-template <int NX, int NU>
-__device__ __forceinline__ void load_ip_bounds(const SolveParams& p, double* yl, double* yu) {
+template <int NX, int NU, bool IB = false>
+__device__ __forceinline__ void load_ip_bounds(const SolveParams& p, int64_t inst, double* yl, double* yu) {
+    // control part: the instance's own row under IB (load_bounds); the state bounds are per handle
+    const double* const ulo = (IB && p.u_lb) ? p.u_lb + inst * (int64_t)p.b_stride : p.u_lb;
+    const double* const uhi = (IB && p.u_ub) ? p.u_ub + inst * (int64_t)p.b_stride : p.u_ub;
 #pragma unroll
     for (int j = 0; j < NX + NU; ++j) {
-        const double* lo = j < NX ? (p.x_bounded ? p.x_lb : nullptr) : p.u_lb;
-        const double* hi = j < NX ? (p.x_bounded ? p.x_ub : nullptr) : p.u_ub;
+        const double* lo = j < NX ? (p.x_bounded ? p.x_lb : nullptr) : ulo;
+        const double* hi = j < NX ? (p.x_bounded ? p.x_ub : nullptr) : uhi;
         const int i = j < NX ? j : j - NX;
         yl[j] = (lo && lo[i] > -1e19) ? lo[i] : -INFINITY;
         yu[j] = (hi && hi[i] < 1e19) ? hi[i] : INFINITY;
@@ -499,7 +528,7 @@ __global__ __launch_bounds__(64, MMPC_WAVES_PER_SIMD) void sqp_wave_kernel(Solve
     const double hstep = p.h;
 
     double lbv[NU], ubv[NU];
-    load_bounds<NU, BOUNDED>(p, lbv, ubv);
+    load_bounds<NU, BOUNDED, true>(p, inst, lbv, ubv);   // one instance per wave: the row address is wave-uniform
     // bounds of the control a Hessian-row lane owns (input lane % NU)
     double lb_row = lbv[0], ub_row = ubv[0];
 #pragma unroll

@@ -11,7 +11,10 @@
 //     tick i, the download of tick i's solution (from a per-slot device copy, so the next solve may overwrite V)
 //     overlaps the solve of tick i+1; results are published when their download event completes;
 //   * optional warm-start shift (off by default, as the reference): V moved k stages earlier, k = elapsed
-//     time / step, by two strided device copies.
+//     time / step, by two strided device copies;
+//   * control limits for all instances or per instance (update_control_limits): B reference controllers have B limit
+//     sets that change independently (ModelControl.cpp:205-209); the per-instance table [B][nu] x 2 is packed into the
+//     tick's staging slot and travels in its single H2D (mmpc_solve_batch_bounds, bounds_stride = nu).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -63,7 +66,14 @@ public:
     double mean_tick_ms() const;                                      // worker: enqueue -> published
 
     void update_weights(std::vector<double> Q = {}, std::vector<double> R = {}, std::vector<double> Rm = {});
+    // the control limits of ALL instances (ModelControl::update_control_limits for every controller of the batch);
+    // returns the object to one shared box after per-instance updates
     void update_control_limits(std::vector<double> u_min, std::vector<double> u_max);
+    // the control limits of instance b alone -- ModelControl::update_control_limits (ModelControl.cpp:205-209) of that
+    // one controller: derated actuators, limits that follow speed or temperature, mixed hardware.  The other instances
+    // keep theirs.  The table travels in the tick's single H2D (mmpc_solve_batch_bounds, bounds_stride = nu); a tick
+    // uses the limits in force when it is enqueued.  Additive: not part of the reference's interface.
+    void update_control_limits(int64_t b, std::vector<double> u_min, std::vector<double> u_max);
     // move the warm start k = round((t - t_prev) / step) stages earlier before each solve (default false)
     void set_warm_start_shift(bool on) { m_shift = on; }
     // barrier rule of the solves with finite state bounds (x_min / x_max of the model file): 0 = IPOPT's monotone rule
@@ -94,6 +104,8 @@ private:
     std::mutex m_weights_mutex;
     std::vector<double> m_Q, m_R, m_Rm;
     std::mutex m_control_limits_mutex;
+    bool m_limits_per_instance = false;               // under m_control_limits_mutex, as the two tables
+    std::vector<double> m_u_min_table, m_u_max_table;  // [B*nu] while per-instance limits are in use
 
     std::mutex m_solve_mutex;  // one tick pipeline at a time (calc_u vs the worker)
     double m_tick_ms_sum = 0.0;

@@ -73,6 +73,14 @@ public:
                                                   const std::vector<std::vector<double>>& controls,
                                                   const std::vector<std::vector<double>>& trajs,
                                                   std::vector<int>* status = nullptr);
+    // the same with the control limits of each instance: u_mins / u_maxs hold B rows of num_u entries (what B
+    // controllers would each have set with update_control_limits); this object's own limits are not used
+    std::vector<std::vector<double>> calc_u_batch(const std::vector<std::vector<double>>& states,
+                                                  const std::vector<std::vector<double>>& controls,
+                                                  const std::vector<std::vector<double>>& trajs,
+                                                  const std::vector<std::vector<double>>& u_mins,
+                                                  const std::vector<std::vector<double>>& u_maxs,
+                                                  std::vector<int>* status = nullptr);
 
 private:
     std::shared_ptr<detail::ModelLibrary> m_backend;  // C-ABI of the model's library (dll_filepath)
@@ -101,6 +109,13 @@ private:
 
     void format_outputs(const std::vector<double>& opt_output);
     std::vector<double> packed_weights();
+    // calc_u_batch with this object's limits (u_mins == nullptr) or a row of limits per instance
+    std::vector<std::vector<double>> calc_u_batch_impl(const std::vector<std::vector<double>>& states,
+                                                       const std::vector<std::vector<double>>& controls,
+                                                       const std::vector<std::vector<double>>& trajs,
+                                                       const std::vector<std::vector<double>>* u_mins,
+                                                       const std::vector<std::vector<double>>* u_maxs,
+                                                       std::vector<int>* status);
 };
 
 }  // namespace mpc

@@ -33,8 +33,9 @@ struct BatchModelControl::Impl {
     int nx = 0, nu = 0, N = 0, NV = 0;
     double step = 0.0;
     int64_t B = 0;
-    // per-slot input block (device and pinned host): x0 [B nx] | u_prev [B nu] | traj [B N nx] | Q R Rm | lb | ub
-    size_t off_up = 0, off_tr = 0, off_w = 0, off_lb = 0, off_ub = 0, in_doubles = 0;
+    // per-slot input block (device and pinned host): x0 [B nx] | u_prev [B nu] | traj [B N nx] | Q R Rm | lb | ub |
+    // lb table [B nu] | ub table [B nu] (per-instance limits: uploaded, in the same single H2D, only while in use)
+    size_t off_up = 0, off_tr = 0, off_w = 0, off_lb = 0, off_ub = 0, off_lbt = 0, off_ubt = 0, in_doubles = 0;
     double* d_in[2] = {nullptr, nullptr};
     double* h_in[2] = {nullptr, nullptr};
     bool bounded[2] = {false, false};
@@ -93,7 +94,9 @@ BatchModelControl::BatchModelControl(std::string model_name, int64_t B, std::vec
     m->off_w = m->off_tr + b * N * nx;
     m->off_lb = m->off_w + nx + 2 * nu;
     m->off_ub = m->off_lb + nu;
-    m->in_doubles = m->off_ub + nu;
+    m->off_lbt = m->off_ub + nu;
+    m->off_ubt = m->off_lbt + b * nu;
+    m->in_doubles = m->off_ubt + b * nu;
     HIPC(hipStreamCreateWithFlags(&m->compute, hipStreamNonBlocking));
     HIPC(hipStreamCreateWithFlags(&m->copy, hipStreamNonBlocking));
     HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_V), b * NV * sizeof(double)));
@@ -161,20 +164,30 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
         std::copy(m_R.begin(), m_R.end(), in + I.off_w + nx);
         std::copy(m_Rm.begin(), m_Rm.end(), in + I.off_w + nx + nu);
     }
-    bool finite = false;
+    bool finite = false, per_instance = false;
     {
-        std::lock_guard<std::mutex> lg(m_control_limits_mutex);  // ModelControl.cpp:148-154
+        // the limits of this tick are those in force now, when it is enqueued: a later update_control_limits changes
+        // the next tick, never a solve already queued (ModelControl.cpp:148-154 reads them under this mutex per tick)
+        std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+        per_instance = m_limits_per_instance;
+        if (per_instance) {
+            std::copy(m_u_min_table.begin(), m_u_min_table.end(), in + I.off_lbt);
+            std::copy(m_u_max_table.begin(), m_u_max_table.end(), in + I.off_ubt);
+            for (size_t i = 0; i < b * nu; ++i) finite |= m_u_min_table[i] > -1e19 || m_u_max_table[i] < 1e19;
+        }
         for (size_t c = 0; c < nu; ++c) {
             const double lo = c < model_parameters.u_min.size() ? model_parameters.u_min[c] : -10e30;
             const double hi = c < model_parameters.u_max.size() ? model_parameters.u_max[c] : 10e30;
             in[I.off_lb + c] = lo;
             in[I.off_ub + c] = hi;
-            finite |= lo > -1e19 || hi < 1e19;  // IPOPT: |bound| >= 1e19 is infinite
+            if (!per_instance) finite |= lo > -1e19 || hi < 1e19;  // IPOPT: |bound| >= 1e19 is infinite
         }
     }
     I.bounded[slot] = finite;
     double* d = I.d_in[slot];
-    HIPC(hipMemcpyAsync(d, in, I.in_doubles * sizeof(double), hipMemcpyHostToDevice, I.copy));
+    // one H2D per tick: the per-instance tables lie at the end of the slot and travel only while they are in use
+    const size_t up_doubles = per_instance ? I.in_doubles : I.off_lbt;
+    HIPC(hipMemcpyAsync(d, in, up_doubles * sizeof(double), hipMemcpyHostToDevice, I.copy));
     HIPC(hipEventRecord(I.h2d_done[slot], I.copy));
     HIPC(hipStreamWaitEvent(I.compute, I.h2d_done[slot], 0));
     if (m_shift && I.have_prev) {  // warm start moved k stages earlier (the tail keeps its old values)
@@ -190,10 +203,12 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
     }
     I.have_prev = true;
     I.prev_time = time;
-    I.check(I.lib->solve_batch(I.h, I.B, d, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
-                               finite ? d + I.off_lb : nullptr, finite ? d + I.off_ub : nullptr, I.d_V, I.d_st[slot],
-                               I.d_it[slot], nullptr, I.compute),
-            "mmpc_solve_batch");
+    const size_t olb = per_instance ? I.off_lbt : I.off_lb, oub = per_instance ? I.off_ubt : I.off_ub;
+    I.check(I.lib->solve_batch_bounds(I.h, I.B, d, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
+                                      finite ? d + olb : nullptr, finite ? d + oub : nullptr,
+                                      per_instance ? static_cast<int64_t>(nu) : 0, I.d_V, I.d_st[slot], I.d_it[slot],
+                                      nullptr, nullptr, I.compute),
+            "mmpc_solve_batch_bounds");
     // the next solve updates d_V in place: download from a per-slot copy
     HIPC(hipMemcpyAsync(I.d_Vout[slot], I.d_V, b * NV * sizeof(double), hipMemcpyDeviceToDevice, I.compute));
     HIPC(hipEventRecord(I.solved[slot], I.compute));
@@ -364,6 +379,27 @@ void BatchModelControl::update_control_limits(std::vector<double> u_min, std::ve
     std::lock_guard<std::mutex> lg(m_control_limits_mutex);
     model_parameters.u_min = u_min;
     model_parameters.u_max = u_max;
+    m_limits_per_instance = false;   // all instances: back to the one shared box
+}
+
+void BatchModelControl::update_control_limits(int64_t b, std::vector<double> u_min, std::vector<double> u_max) {
+    if (b < 0 || b >= m_B) throw std::out_of_range("update_control_limits: instance index");
+    const size_t nu = m->nu;
+    if (u_min.size() != nu || u_max.size() != nu)
+        throw std::invalid_argument("update_control_limits: u_min, u_max must have num_u entries");
+    std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+    if (!m_limits_per_instance) {   // every instance starts from the shared limits (ModelControl.cpp:37-50)
+        m_u_min_table.resize(static_cast<size_t>(m_B) * nu);
+        m_u_max_table.resize(static_cast<size_t>(m_B) * nu);
+        for (size_t i = 0; i < static_cast<size_t>(m_B); ++i)
+            for (size_t c = 0; c < nu; ++c) {
+                m_u_min_table[i * nu + c] = c < model_parameters.u_min.size() ? model_parameters.u_min[c] : -10e30;
+                m_u_max_table[i * nu + c] = c < model_parameters.u_max.size() ? model_parameters.u_max[c] : 10e30;
+            }
+        m_limits_per_instance = true;
+    }
+    std::copy(u_min.begin(), u_min.end(), m_u_min_table.begin() + static_cast<size_t>(b) * nu);
+    std::copy(u_max.begin(), u_max.end(), m_u_max_table.begin() + static_cast<size_t>(b) * nu);
 }
 
 void BatchModelControl::set_barrier_rule(int rule) {

@@ -92,9 +92,29 @@ std::vector<std::vector<double>> ModelControl::calc_u_batch(const std::vector<st
                                                             const std::vector<std::vector<double>>& controls,
                                                             const std::vector<std::vector<double>>& trajs,
                                                             std::vector<int>* status) {
+    return calc_u_batch_impl(states, controls, trajs, nullptr, nullptr, status);
+}
+
+std::vector<std::vector<double>> ModelControl::calc_u_batch(const std::vector<std::vector<double>>& states,
+                                                            const std::vector<std::vector<double>>& controls,
+                                                            const std::vector<std::vector<double>>& trajs,
+                                                            const std::vector<std::vector<double>>& u_mins,
+                                                            const std::vector<std::vector<double>>& u_maxs,
+                                                            std::vector<int>* status) {
+    return calc_u_batch_impl(states, controls, trajs, &u_mins, &u_maxs, status);
+}
+
+std::vector<std::vector<double>> ModelControl::calc_u_batch_impl(const std::vector<std::vector<double>>& states,
+                                                                 const std::vector<std::vector<double>>& controls,
+                                                                 const std::vector<std::vector<double>>& trajs,
+                                                                 const std::vector<std::vector<double>>* u_mins,
+                                                                 const std::vector<std::vector<double>>* u_maxs,
+                                                                 std::vector<int>* status) {
     const size_t nx = model_parameters.num_x, nu = model_parameters.num_u, N = model_parameters.num_shooting_nodes;
     const size_t B = states.size();
     if (controls.size() != B || trajs.size() != B) throw std::invalid_argument("calc_u_batch: batch size mismatch");
+    if (u_mins && (u_mins->size() != B || u_maxs->size() != B))
+        throw std::invalid_argument("calc_u_batch: one row of control limits per instance");
     std::vector<double> x0, up, tr, V(B * m_V.size(), 0.0);
     for (size_t b = 0; b < B; ++b) {
         if (states[b].size() != nx || controls[b].size() != nu || trajs[b].size() != N * nx)
@@ -105,17 +125,28 @@ std::vector<std::vector<double>> ModelControl::calc_u_batch(const std::vector<st
     }
     const std::vector<double> w = packed_weights();
     std::vector<double> lb, ub;
-    {
+    int64_t bounds_stride = 0;
+    if (u_mins) {   // instance-major rows, bounds_stride = num_u
+        for (size_t b = 0; b < B; ++b) {
+            if ((*u_mins)[b].size() != nu || (*u_maxs)[b].size() != nu)
+                throw std::invalid_argument("calc_u_batch: control limits need num_u entries per instance");
+            lb.insert(lb.end(), (*u_mins)[b].begin(), (*u_mins)[b].end());
+            ub.insert(ub.end(), (*u_maxs)[b].begin(), (*u_maxs)[b].end());
+        }
+        bounds_stride = static_cast<int64_t>(nu);
+    } else {
         std::lock_guard<std::mutex> lg(m_control_limits_mutex);  // the limits calc_u enforces (ModelControl.cpp:148-154)
         lb = model_parameters.u_min;
         ub = model_parameters.u_max;
     }
+    const size_t nb = u_mins ? B * nu : nu;   // entries a complete set of limits has
     std::vector<int32_t> st(B, -1), it(B, 0);
     std::vector<double> kkt(B, 0.0);
-    m_backend->check(m_backend->solve_batch_host(m_handle, static_cast<int64_t>(B), x0.data(), up.data(), tr.data(), w.data(), 0,
-                                lb.size() == nu ? lb.data() : nullptr, ub.size() == nu ? ub.data() : nullptr,
-                                V.data(), st.data(), it.data(), kkt.data()),
-          "mmpc_solve_batch_host");
+    m_backend->check(m_backend->solve_batch_host_bounds(
+                         m_handle, static_cast<int64_t>(B), x0.data(), up.data(), tr.data(), w.data(), 0,
+                         lb.size() == nb ? lb.data() : nullptr, ub.size() == nb ? ub.data() : nullptr, bounds_stride,
+                         V.data(), st.data(), it.data(), kkt.data()),
+                     "mmpc_solve_batch_host_bounds");
     std::vector<std::vector<double>> out(B);
     for (size_t b = 0; b < B; ++b) out[b].assign(V.begin() + b * m_V.size(), V.begin() + (b + 1) * m_V.size());
     if (status) status->assign(st.begin(), st.end());

@@ -26,6 +26,9 @@ struct ModelLibrary {
     decltype(&mmpc_get_model_info) get_model_info = &mmpc_get_model_info;
     decltype(&mmpc_solve_batch_host) solve_batch_host = &mmpc_solve_batch_host;
     decltype(&mmpc_solve_batch) solve_batch = &mmpc_solve_batch;
+    // per-instance control limits (bounds_stride): the batched mirror of update_control_limits per controller
+    decltype(&mmpc_solve_batch_bounds) solve_batch_bounds = &mmpc_solve_batch_bounds;
+    decltype(&mmpc_solve_batch_host_bounds) solve_batch_host_bounds = &mmpc_solve_batch_host_bounds;
     decltype(&mmpc_reserve_workspace) reserve_workspace = &mmpc_reserve_workspace;
     decltype(&mmpc_set_barrier_rule) set_barrier_rule = &mmpc_set_barrier_rule;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
@@ -71,6 +74,8 @@ struct ModelLibrary {
         b->bind(b->get_model_info, "mmpc_get_model_info");
         b->bind(b->solve_batch_host, "mmpc_solve_batch_host");
         b->bind(b->solve_batch, "mmpc_solve_batch");
+        b->bind(b->solve_batch_bounds, "mmpc_solve_batch_bounds");
+        b->bind(b->solve_batch_host_bounds, "mmpc_solve_batch_host_bounds");
         b->bind(b->reserve_workspace, "mmpc_reserve_workspace");
         b->bind(b->set_barrier_rule, "mmpc_set_barrier_rule");
         b->bind(b->last_error, "mmpc_last_error");

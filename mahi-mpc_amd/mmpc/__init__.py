@@ -109,6 +109,13 @@ def lib(path: str | None = None):
         L.mmpc_solve_batch.argtypes = [_vp, C.c_int64] + [_vp] * 4 + [C.c_int64] + [_vp] * 7
         L.mmpc_solve_batch_host.argtypes = [_vp, C.c_int64] + [_vp] * 4 + [C.c_int64] + [_vp] * 6
         L.mmpc_solve_batch_u0.argtypes = [_vp, C.c_int64] + [_vp] * 4 + [C.c_int64] + [_vp] * 8
+        # per-instance control bounds: the signatures above plus bounds_stride after u_ub
+        L.mmpc_solve_batch_bounds.argtypes = [_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64] + [_vp] * 6
+        L.mmpc_solve_batch_host_bounds.argtypes = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64]
+                                                   + [_vp] * 4)
+        L.mmpc_multi_solve_batch_host_bounds.argtypes = L.mmpc_solve_batch_host_bounds.argtypes
+        L.mmpc_multi_solve_batch_rccl_bounds.argtypes = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64]
+                                                         + [_vp] * 5)
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -246,6 +253,24 @@ def _f64(a, shape=None):
     return a
 
 
+def _host_bounds(u_lb, u_ub, B, nu):
+    """(lb, ub, bounds_stride) of host control bounds: [nu] rows are shared (stride 0), [B, nu] arrays are per
+    instance (stride nu); when only one of the two is 2-D the other is repeated, since one stride serves both."""
+    lb = None if u_lb is None else _f64(u_lb)
+    ub = None if u_ub is None else _f64(u_ub)
+    if not any(a is not None and a.ndim == 2 for a in (lb, ub)):
+        return lb, ub, 0
+    def rows(a):
+        if a is None:
+            return None
+        if a.ndim == 1:
+            a = np.broadcast_to(a.reshape(1, nu), (B, nu))
+        if a.shape != (B, nu):
+            raise ValueError(f"control bounds of shape {a.shape}: expected ({nu},) or ({B}, {nu})")
+        return np.ascontiguousarray(a)
+    return rows(lb), rows(ub), nu
+
+
 class Solver:
     """One loaded model (the reference's ModelControl without the thread/bookkeeping)."""
 
@@ -314,10 +339,17 @@ class Solver:
 
     # ---- device-pointer API (torch tensors on the GPU or raw addresses) ----
     def solve_batch(self, B, x0, u_prev, traj, weights, V, status=None, iters=None, kkt=None,
-                    weights_stride=0, u_lb=None, u_ub=None, stream=None, u0=None):
+                    weights_stride=0, u_lb=None, u_ub=None, stream=None, u0=None, bounds_stride=0):
         """Device-pointer solve (stream-ordered).  u0: optional [B][nu] output of u_0* (mmpc_solve_batch_u0);
-        u0 / status / iters may be HostBuffer views (results stored by the kernel straight into host memory)."""
-        if u0 is None:
+        u0 / status / iters may be HostBuffer views (results stored by the kernel straight into host memory).
+        bounds_stride: 0 = u_lb / u_ub are [nu], shared; >= nu = instance b's row starts at b * bounds_stride
+        (mmpc_solve_batch_bounds)."""
+        if bounds_stride:
+            self._check(self._L.mmpc_solve_batch_bounds(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                        weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                        _ptr(V), _ptr(status), _ptr(iters), _ptr(kkt), _ptr(u0),
+                                                        stream))
+        elif u0 is None:
             self._check(self._L.mmpc_solve_batch(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
                                                  weights_stride, _ptr(u_lb), _ptr(u_ub), _ptr(V), _ptr(status),
                                                  _ptr(iters), _ptr(kkt), stream))
@@ -360,10 +392,10 @@ class Solver:
         st = np.zeros(B, np.int32)
         it = np.zeros(B, np.int32)
         kkt = np.zeros(B)
-        lb = None if u_lb is None else _f64(u_lb)
-        ub = None if u_ub is None else _f64(u_ub)
-        self._check(self._L.mmpc_solve_batch_host(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights), ws,
-                                           _ptr(lb), _ptr(ub), _ptr(V), _ptr(st), _ptr(it), _ptr(kkt)))
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)   # [nu] shared, or [B, nu] per instance
+        self._check(self._L.mmpc_solve_batch_host_bounds(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                         ws, _ptr(lb), _ptr(ub), bs, _ptr(V), _ptr(st), _ptr(it),
+                                                         _ptr(kkt)))
         return dict(V=V, status=st, iters=it, kkt=kkt)
 
     def set_state_bounds(self, x_lb=None, x_ub=None):
@@ -449,27 +481,35 @@ class MultiSolver:
         ws = 0 if weights.ndim == 1 else weights.shape[-1]
         V = np.zeros((B, NV)) if V is None else _f64(V, (B, NV)).copy()
         st, it, kkt = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
-        lb = None if u_lb is None else _f64(u_lb)
-        ub = None if u_ub is None else _f64(u_ub)
-        _check(self._L.mmpc_multi_solve_batch_host(self._m, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights), ws,
-                                                   _ptr(lb), _ptr(ub), _ptr(V), _ptr(st), _ptr(it), _ptr(kkt)), self._L)
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)   # [nu] shared, or [B, nu] per instance
+        _check(self._L.mmpc_multi_solve_batch_host_bounds(self._m, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                          ws, _ptr(lb), _ptr(ub), bs, _ptr(V), _ptr(st), _ptr(it),
+                                                          _ptr(kkt)), self._L)
         return dict(V=V, status=st, iters=it, kkt=kkt)
 
     def solve_batch_rccl(self, x0, u_prev, traj, weights, V, status=None, iters=None, kkt=None, u_lb=None,
-                         u_ub=None, weights_stride=None, stream=None):
-        """mmpc_multi_solve_batch_rccl: torch tensors on the FIRST device of the handle (fp64, contiguous; weights
-        [nx+2nu] shared or [B][nx+2nu], or a flat buffer with an explicit weights_stride); V is updated in place,
-        status / iters (int32) / kkt filled if given.  stream: the hipStream_t (int) the inputs were produced on --
-        default torch's current stream of x0's device."""
+                         u_ub=None, weights_stride=None, stream=None, bounds_stride=None):
+        """mmpc_multi_solve_batch_rccl_bounds: torch tensors on the FIRST device of the handle (fp64, contiguous;
+        weights [nx+2nu] shared or [B][nx+2nu], or a flat buffer with an explicit weights_stride; u_lb / u_ub [nu]
+        shared or [B][nu], or flat buffers with an explicit bounds_stride); V is updated in place, status / iters
+        (int32) / kkt filled if given.  stream: the hipStream_t (int) the inputs were produced on -- default torch's
+        current stream of x0's device."""
         B = x0.shape[0]
         ws = (0 if weights.dim() == 1 else weights.shape[-1]) if weights_stride is None else int(weights_stride)
+        if bounds_stride is None:
+            two_d = [t for t in (u_lb, u_ub) if t is not None and t.dim() == 2]
+            if two_d and any(t is not None and t.dim() != 2 for t in (u_lb, u_ub)):
+                raise ValueError("u_lb and u_ub: both [nu] or both [B, nu] (one stride serves both)")
+            bs = two_d[0].shape[-1] if two_d else 0
+        else:
+            bs = int(bounds_stride)
         if stream is None:
             import torch
             stream = torch.cuda.current_stream(x0.device).cuda_stream
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self._L.mmpc_multi_solve_batch_rccl(self._m, B, p(x0), p(u_prev), p(traj), p(weights), ws, p(u_lb),
-                                                   p(u_ub), p(V), p(status), p(iters), p(kkt),
-                                                   C.c_void_p(stream) if stream else None), self._L)
+        _check(self._L.mmpc_multi_solve_batch_rccl_bounds(self._m, B, p(x0), p(u_prev), p(traj), p(weights), ws,
+                                                          p(u_lb), p(u_ub), bs, p(V), p(status), p(iters), p(kkt),
+                                                          C.c_void_p(stream) if stream else None), self._L)
 
     def close(self):
         if getattr(self, "_m", None):

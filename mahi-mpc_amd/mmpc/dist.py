@@ -156,22 +156,31 @@ def solve_rank0_batch(solver, x0=None, u_prev=None, traj=None, weights=None, V=N
     world = dist.get_world_size() if _pg_ready() else 1
     rank = dist.get_rank() if _pg_ready() else 0
     nx, nu, N, NV = solver.nx, solver.nu, solver.N, solver.NV
-    meta = torch.zeros(5, dtype=torch.int64, device=device)
+    meta = torch.zeros(6, dtype=torch.int64, device=device)
     if rank == 0:
         meta[0] = x0.shape[0]
         meta[1] = int(V is not None)
         meta[2] = int(u_lb is not None)
         meta[3] = int(u_ub is not None)
         meta[4] = int(weights_stride)
+        dims = {t.dim() for t in (u_lb, u_ub) if t is not None}
+        if len(dims) > 1:
+            raise ValueError("u_lb and u_ub: both [nu] or both [B, nu] (one stride serves both)")
+        meta[5] = nu if dims == {2} else 0   # per-instance bounds [B, nu]: scattered like the instances
     if _multi():
         dist.broadcast(meta, src=0)
-    B, has_V, has_lb, has_ub, ws = (int(v) for v in meta.tolist())
+    B, has_V, has_lb, has_ub, ws, bs = (int(v) for v in meta.tolist())
     f64 = dict(dtype=torch.float64, device=device)
     if rank != 0:
         weights = None if ws else torch.empty(nx + 2 * nu, **f64)
-        u_lb = torch.empty(nu, **f64) if has_lb else None
-        u_ub = torch.empty(nu, **f64) if has_ub else None
-    broadcast_shared(None if ws else weights, u_lb, u_ub)
+        u_lb = torch.empty(nu, **f64) if has_lb and not bs else None
+        u_ub = torch.empty(nu, **f64) if has_ub and not bs else None
+    if bs:   # the same ragged shards as the instances
+        u_lb = scatter_rows(u_lb, B, (nu,), torch.float64, device).contiguous() if has_lb else None
+        u_ub = scatter_rows(u_ub, B, (nu,), torch.float64, device).contiguous() if has_ub else None
+        broadcast_shared(None if ws else weights)
+    else:
+        broadcast_shared(None if ws else weights, u_lb, u_ub)
     w_loc = scatter_rows(weights, B, (ws,), torch.float64, device) if ws else weights
     x_loc = scatter_rows(x0, B, (nx,), torch.float64, device)
     u_loc = scatter_rows(u_prev, B, (nu,), torch.float64, device)
@@ -184,7 +193,8 @@ def solve_rank0_batch(solver, x0=None, u_prev=None, traj=None, weights=None, V=N
     kk = torch.empty(n, **f64)
     if n:
         solver.solve_batch(n, x_loc.contiguous(), u_loc.contiguous(), t_loc.contiguous(), w_loc.contiguous(),
-                           V_loc, st, it, kk, weights_stride=ws, u_lb=u_lb, u_ub=u_ub)
+                           V_loc, st, it, kk, weights_stride=ws, u_lb=u_lb, u_ub=u_ub,
+                           **({"bounds_stride": bs} if bs else {}))
     res = torch.cat([V_loc, st.double()[:, None], it.double()[:, None], kk[:, None]], 1)
     full = gather_rows(res, B)
     if full is None:
