@@ -299,6 +299,48 @@ int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, co
                                  const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
                                  int32_t* status, int32_t* iters, double* kkt_res);
 
+/* ---- committed controls: pin the leading controls of the horizon (additive to ABI 6) ----
+ * A controller that solves while the plant keeps moving (ModelControl::start_calc, ModelControl.cpp:83-112) publishes a
+ * plan whose first controls have already been applied.  The reference began the cure -- ModelControl.hpp:79 keeps
+ * m_num_control_inputs_saved and ModelControl.cpp:165-171 writes the first m controls of the last solution into lbx and
+ * ubx -- but m is 0 without a setter and the next calc_u overwrites those bounds (:150-153).  The *_pinned entry points
+ * pose what it meant: the same NLP with u_k = u_pin[b][k] for k < n_pin (lbx = ubx on those entries).  Each is the
+ * *_bounds entry point of the same name plus `u_pin, n_pin` after bounds_stride.
+ *   u_pin    [B][n_pin][nu], dense, instance-major (DEVICE memory for mmpc_solve_batch_pinned, host memory for the
+ *            host entries): B controllers have B plans.  May be NULL when n_pin == 0.
+ *   n_pin    0 .. N - 1.  0 forwards to the *_bounds entry point (the same bits as without pins).  n_pin < 0,
+ *            n_pin > N - 1, or n_pin > 0 with u_pin == NULL: MMPC_ERR_INVALID_ARG, mmpc_last_error names `n_pin` /
+ *            `u_pin`.  A linear-mode model (is_linear) with n_pin > 0: MMPC_ERR_UNSUPPORTED -- the reference linearises
+ *            at the measured (x_0, u_prev), the reduced problem below would linearise at x_m; it is not run under the
+ *            other meaning.  All checked from the arguments alone, before any device call, as bounds_stride is.
+ * The pins override the control box as lbx = ubx would: a pinned value outside [u_lb, u_ub] is kept, not projected, and
+ * gets no barrier slack.
+ * How it is solved: with u_0..u_{m-1} fixed, x_1..x_m follow from x_0 by m Euler steps, and the rest is
+ * the horizon-(N - m) problem from x_m with u_prev' = u_pin[b][m-1] and the targets traj[b][m:], solved by the same
+ * kernels (the KKT solver and Hessian are resolved for the handle's own N; weights, control and state bounds, barrier
+ * rule, init_states -- applied to the tail: HOLD_X0 holds at x_m -- tail_* and factor_fp32 act as on any solve).
+ * What is written where: V_inout[b] = [x_0, u_pin_0, x_1, .., u_pin_{m-1}, x_m | the tail solution]; the warm start is
+ * read from V_inout[b] from offset m (nx + nu) on; u0_out[b] = u_pin[b][0], the control in force now
+ * (V[b][nx : nx + nu]); status / iters / kkt_res are those of the tail solve.  The x_1..x_m implied by the pins are NOT
+ * checked against the state bounds (they are no decision of this solve); with finite state bounds an x_{m+1} that
+ * cannot reach the box reports failure per instance, as an x_0 outside a position box does.  A non-finite pin gives
+ * its own instance a non-converged status and leaves the others untouched.
+ * Staging: B (nx + nu + (N - 1) nx + NV(N - 1)) doubles of the handle's workspace; mmpc_reserve_workspace(B) includes
+ * them (whether or not pins are ever used), after which a pinned solve allocates nothing and can be captured in a
+ * hipGraph.  The staging is per handle like the Riccati workspace -- also under MMPC_KKT_CONDENSED, whose unpinned
+ * solves use no workspace: pinned solves of one handle go to one stream at a time.  The RCCL entry and mmpc/dist.py
+ * take no pins (out of scope). */
+int mmpc_solve_batch_pinned(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                            const double* traj, const double* weights, int64_t weights_stride,
+                            const double* u_lb, const double* u_ub, int64_t bounds_stride, const double* u_pin,
+                            int32_t n_pin, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res,
+                            double* u0_out, void* stream);
+/* HOST pointers, synchronous; the pins travel with the other inputs */
+int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                                 const double* traj, const double* weights, int64_t weights_stride,
+                                 const double* u_lb, const double* u_ub, int64_t bounds_stride, const double* u_pin,
+                                 int32_t n_pin, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res);
+
 /* Continuous-time linearisation at (x[b], u[b]): A = df/dx [nx*nx], B = df/du [nx*nu]
  * column-major, xdot = f(x,u) [nx].  DEVICE pointers; any output may be NULL. */
 int mmpc_linearize_batch(mmpc_handle* h, int64_t B, const double* x, const double* u,
@@ -387,7 +429,14 @@ int mmpc_multi_solve_batch_rccl_bounds(mmpc_multi* m, int64_t B, const double* x
                                        const double* traj, const double* weights, int64_t weights_stride,
                                        const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
                                        int32_t* status, int32_t* iters, double* kkt_res, void* stream);
-/* the version of the RCCL library the call above loads (ncclGetVersion, e.g. 22606), MMPC_ERR_UNSUPPORTED if none */
+/* mmpc_multi_solve_batch_host_bounds with committed controls (u_pin [B][n_pin][nu] host memory, n_pin: see
+ * mmpc_solve_batch_pinned): shard g gets the rows from first * n_pin * nu on.  The RCCL entry takes no pins. */
+int mmpc_multi_solve_batch_host_pinned(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride,
+                                       const double* u_pin, int32_t n_pin, double* V_inout, int32_t* status,
+                                       int32_t* iters, double* kkt_res);
+/* the version of the RCCL library the RCCL entries load (ncclGetVersion, e.g. 22606), MMPC_ERR_UNSUPPORTED if none */
 int mmpc_rccl_version(int32_t* version);
 
 const char* mmpc_status_string(int32_t status);

@@ -315,6 +315,81 @@ __global__ __launch_bounds__(256) void nlp_eval_kernel(int64_t B, int N, double 
     if (ginf) ginf[b] = gm;
 }
 
+// ---- committed controls (mmpc_solve_batch_pinned) ----
+// With u_0..u_{m-1} fixed to the caller's values (the lbx = ubx = u the reference's ModelControl.cpp:165-171 meant to
+// pose), x_1..x_m are fixed too and the rest is the horizon-(N - m) problem from x_m with u_prev' = u_{m-1} and the
+// targets traj[m:].  The three kernels below reduce a batch to that problem in a staging area and put its solution
+// back; the solver kernels run unchanged on the staging arrays with SolveParams::N = N - m.
+//
+// Prologue 1: one lane per instance, m serial Euler steps x_{k+1} = x_k + h f(x_k, u_k) with the model's value
+// evaluation (as nlp_eval_kernel forms F).  Writes x_0..x_m and the pins into the head of V[b], and x_m / u_{m-1} as
+// the tail problem's x0' / u_prev'.
+template <class Model>
+__global__ __launch_bounds__(256) void pin_rollout_kernel(int64_t B, int N, int m, double h,
+                                                          const double* __restrict__ x0,
+                                                          const double* __restrict__ u_pin, double* __restrict__ V,
+                                                          double* __restrict__ x0s, double* __restrict__ ups) {
+    constexpr int NX = Model::NX, NU = Model::NU, ND = NX + NU;
+    const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t NV = (int64_t)NX * (N + 1) + (int64_t)NU * N;
+    double* v = V + b * NV;
+    const double* pin = u_pin + b * (int64_t)m * NU;
+    double xk[NX], uk[NU] = {}, xd[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) xk[r] = x0[b * NX + r];
+    for (int k = 0; k < m; ++k) {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) uk[c] = pin[k * NU + c];
+#pragma unroll
+        for (int r = 0; r < NX; ++r) v[k * ND + r] = xk[r];
+#pragma unroll
+        for (int c = 0; c < NU; ++c) v[k * ND + NX + c] = uk[c];
+        model_eval<Model>(xk, uk, xd);
+#pragma unroll
+        for (int r = 0; r < NX; ++r) xk[r] = xk[r] + h * xd[r];
+    }
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {
+        v[m * ND + r] = xk[r];
+        x0s[b * NX + r] = xk[r];
+    }
+#pragma unroll
+    for (int c = 0; c < NU; ++c) ups[b * NU + c] = uk[c];   // m >= 1: the last pin
+}
+
+// Prologue 2: elementwise, consecutive lanes on consecutive doubles of the destination.  trajs [B][N - m][nx] =
+// traj[b][m:], Vs [B][NV(N - m)] = V[b] from offset m (nx + nu) on (its first nx entries are the x_m of prologue 1:
+// same stream, launched after it).  Vs == nullptr (MMPC_INIT_ZERO: the solver does not read V) skips the V part.
+__global__ __launch_bounds__(256) void pin_gather_kernel(int64_t B, int N, int m, int nx, int nu,
+                                                         const double* __restrict__ traj, const double* __restrict__ V,
+                                                         double* __restrict__ trajs, double* __restrict__ Vs) {
+    const int64_t Np = N - m;
+    const int64_t nt = Np * nx, ntf = (int64_t)N * nx;
+    const int64_t nvs = nx * (Np + 1) + nu * Np, nvf = (int64_t)nx * (N + 1) + (int64_t)nu * N;
+    const int64_t row = nt + (Vs ? nvs : 0);
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= B * row) return;
+    const int64_t b = t / row, i = t - b * row;
+    if (i < nt) trajs[b * nt + i] = traj[b * ntf + (int64_t)m * nx + i];
+    else Vs[b * nvs + (i - nt)] = V[b * nvf + (int64_t)m * (nx + nu) + (i - nt)];
+}
+
+// Epilogue: the tail solution back into V[b] from offset m (nx + nu) on, and u0_out[b] = the first pin -- the control
+// in force now, V[b][nx : nx + nu] (u0_out may be nullptr or host-mapped memory).
+__global__ __launch_bounds__(256) void pin_scatter_kernel(int64_t B, int N, int m, int nx, int nu,
+                                                          const double* __restrict__ Vs,
+                                                          const double* __restrict__ u_pin, double* __restrict__ V,
+                                                          double* __restrict__ u0_out) {
+    const int64_t Np = N - m;
+    const int64_t nvs = nx * (Np + 1) + nu * Np, nvf = (int64_t)nx * (N + 1) + (int64_t)nu * N;
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= B * nvs) return;
+    const int64_t b = t / nvs, i = t - b * nvs;
+    V[b * nvf + (int64_t)m * (nx + nu) + i] = Vs[t];
+    if (u0_out && i < nu) u0_out[b * nu + i] = u_pin[b * (int64_t)m * nu + i];
+}
+
 // nlp_grad_f / nlp_jac_g of the generated NLP (ModelGenerator.cpp:238, CasADi generate_dependencies): per
 // instance J, dJ/dV [NV] (V layout) and the nonzero blocks of dg/dV, [dg_k/dx_k | dg_k/du_k] = [I + h f_x | h f_u]
 // (row-major nx x (nx+nu) per stage; dg_k/dx_{k+1} = -I).  Linear mode: F_lin with A*, B* at (x_0, u_prev).
@@ -631,6 +706,16 @@ int model_nq(int model_id) {
     return nq;
 }
 
+// the model at another horizon: a pinned solve (mmpc_solve_batch_pinned) runs the handle's model with N - n_pin
+// shooting nodes, and every host-side size below follows the horizon of the launch (SolveParams::N), not the handle's
+mmpc_model_info with_horizon(const mmpc_model_info& mi, int N) {
+    mmpc_model_info r = mi;
+    r.num_shooting_nodes = N;
+    r.num_v = mi.num_x * (N + 1) + mi.num_u * N;
+    r.num_g = mi.num_x * N;
+    return r;
+}
+
 size_t workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B, bool xb = true) {
     const int64_t blocks = (B + 63) / 64;
     return static_cast<size_t>(lane_ws_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, xb)) * 64u *
@@ -844,11 +929,8 @@ int ensure_workspace_bytes(mmpc_handle* h, size_t bytes, double** out) {
 // (a state-bounded solve's resume workspace follows it: its duals stay in the lane launch's workspace)
 constexpr int kTailMaxSlots = 65536;
 constexpr size_t kTailBytes = 256 + static_cast<size_t>(kTailMaxSlots) * 24;
-size_t solver_workspace_bytes(const mmpc_handle* h, int64_t B) {
-    return (std::max(workspace_bytes(h->info, h->nq, B), group_workspace_bytes(h->info, B)) + 255) / 256 * 256;
-}
-int ensure_workspace(mmpc_handle* h, int64_t B, LaneWork* lw) {
-    return ensure_workspace_bytes(h, solver_workspace_bytes(h, B) + kTailBytes, &lw->ws);
+size_t solver_workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B) {
+    return (std::max(workspace_bytes(mi, nq, B), group_workspace_bytes(mi, B)) + 255) / 256 * 256;
 }
 
 int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
@@ -873,7 +955,7 @@ struct TailPlan {
 };
 TailPlan tail_plan(const mmpc_handle* h, const SolveParams& p, bool bounded, int cu) {
     TailPlan t;
-    const mmpc_model_info& mi = h->info;
+    const mmpc_model_info mi = with_horizon(h->info, p.N);   // the horizon of the launch (a pinned solve's is shorter)
     const bool xb = p.x_bounded != 0;
     if (mi.is_linear || p.trace || cu <= 0) return t;
     if (mi.num_x + mi.num_u >= kGroupLanes) return t;
@@ -932,10 +1014,48 @@ int check_bounds_stride(const mmpc_model_info& mi, int64_t b_stride) {
     return MMPC_OK;
 }
 
+// u_pin / n_pin of the *_pinned entry points.  Pure arithmetic, like check_bounds_stride: checked before any device call.
+int check_pins(const mmpc_model_info& mi, const double* u_pin, int32_t n_pin) {
+    const int N = mi.num_shooting_nodes;
+    if (n_pin < 0 || n_pin > N - 1)
+        return fail(MMPC_ERR_INVALID_ARG, "n_pin must be 0 .. N - 1 (" + std::to_string(N - 1) + "), got " +
+                                              std::to_string(n_pin));
+    if (n_pin > 0 && !u_pin)
+        return fail(MMPC_ERR_INVALID_ARG, "u_pin is NULL with n_pin = " + std::to_string(n_pin));
+    if (n_pin > 0 && mi.is_linear)   // the reference linearises at the measured (x_0, u_prev), the reduction would at x_m
+        return fail(MMPC_ERR_UNSUPPORTED, "n_pin > 0 is not available in linear mode: the model is linearised at the "
+                                          "measured (x_0, u_prev), the reduced problem would linearise at x_m");
+    return MMPC_OK;
+}
+
+// Workspace of a handle with the pinned solves' staging area.  A pinned solve runs the solver at horizon N - m, whose
+// workspace, hand-over list and resume workspace end at an offset that depends on m (the resume slots grow as the
+// stage data shrink), so the staging area lies after the largest of them over every horizon 1..N:
+//   [solver workspace | hand-over list | resume workspace]  (what launch_kernel lays out, any horizon)  | staging
+// staging: x0' [B][nx], u_prev' [B][nu], traj' [B][N - m][nx], V' [B][NV(N - m)]; sized for m = 1, the worst case.
+size_t solve_workspace_bytes_max(const mmpc_handle* h, int64_t B, int cu) {
+    size_t mx = 0;
+    for (int n = 1; n <= h->info.num_shooting_nodes; ++n) {
+        SolveParams p{};
+        p.B = B;
+        p.N = n;
+        p.max_iter = h->opts.max_iter;
+        p.x_bounded = 1;
+        p.is_linear = h->info.is_linear;
+        mx = std::max(mx, solver_workspace_bytes(with_horizon(h->info, n), h->nq, B) + kTailBytes +
+                              tail_plan(h, p, false, cu).xb_ws_bytes);
+    }
+    return (mx + 255) / 256 * 256;
+}
+size_t pin_staging_bytes(const mmpc_model_info& mi, int64_t B) {
+    const size_t nx = mi.num_x, nu = mi.num_u, N1 = mi.num_shooting_nodes > 1 ? mi.num_shooting_nodes - 1 : 0;
+    return static_cast<size_t>(B) * (nx + nu + N1 * nx + nx * (N1 + 1) + nu * N1) * sizeof(double);
+}
+
 int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
                  const double* weights, int64_t w_stride, const double* u_lb, const double* u_ub, double* V,
                  int32_t* status, int32_t* iters, double* kkt, hipStream_t stream, double* trace = nullptr,
-                 double* u0_out = nullptr, int64_t b_stride = 0) {
+                 double* u0_out = nullptr, int64_t b_stride = 0, const double* u_pin = nullptr, int n_pin = 0) {
     const mmpc_model_info& mi = h->info;
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
     if (B == 0) return MMPC_OK;
@@ -991,16 +1111,52 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
             p.x_ub[i] = i < mi.num_x ? h->x_ub[i] : INFINITY;
         }
     }
-    const int solver = resolve_kkt_solver(h, B);
-    return launch_kernel(h, solver, p, bounded, stream, barrier_rule);
+    const int solver = resolve_kkt_solver(h, B);   // for the handle's own N, pinned or not
+    if (n_pin == 0) return launch_kernel(h, solver, p, bounded, stream, barrier_rule);
+    // committed controls: prologue (rollout of the pins, gather of the tail problem), the solve of the staged
+    // horizon-(N - m) problem, epilogue (its solution back into V, u0_out = the first pin)
+    if (int rc = check_pins(mi, u_pin, n_pin)) return rc;
+    if (int rc = query_cu_count(h)) return rc;
+    const int m = n_pin, N = mi.num_shooting_nodes, Np = N - m, nx = mi.num_x, nu = mi.num_u;
+    const size_t base = solve_workspace_bytes_max(h, B, h->cu_count);
+    double* ws = nullptr;
+    if (int rc = ensure_workspace_bytes(h, base + pin_staging_bytes(mi, B), &ws)) return rc;
+    const int64_t nvs = static_cast<int64_t>(nx) * (Np + 1) + static_cast<int64_t>(nu) * Np;
+    double* const x0s = ws + base / sizeof(double);
+    double* const ups = x0s + B * nx;
+    double* const trajs = ups + B * nu;
+    double* const Vs = trajs + B * Np * nx;
+    const int64_t n_gather = B * (static_cast<int64_t>(Np) * nx + (p.init_zero ? 0 : nvs)), n_scatter = B * nvs;
+    if (std::max(n_gather, n_scatter) > 0x7fffffffLL * 256) return fail(MMPC_ERR_INVALID_ARG, "B*N too large");
+    int rc = with_model(mi.model_id, [&](auto* mp) {
+        using M = std::remove_pointer_t<decltype(mp)>;
+        pin_rollout_kernel<M><<<grid1d(B, 256), 256, 0, stream>>>(B, N, m, mi.step_size, x0, u_pin, V, x0s, ups);
+        return static_cast<int>(MMPC_OK);
+    });
+    if (rc) return rc;
+    pin_gather_kernel<<<grid1d(n_gather, 256), 256, 0, stream>>>(B, N, m, nx, nu, traj, V, trajs,
+                                                                  p.init_zero ? nullptr : Vs);
+    MMPC_HIP(hipGetLastError());
+    p.N = Np;
+    p.x0 = x0s;
+    p.u_prev = ups;
+    p.traj = trajs;
+    p.V = Vs;
+    p.u0_out = nullptr;
+    if ((rc = launch_kernel(h, solver, p, bounded, stream, barrier_rule))) return rc;
+    pin_scatter_kernel<<<grid1d(n_scatter, 256), 256, 0, stream>>>(B, N, m, nx, nu, Vs, u_pin, V, u0_out);
+    MMPC_HIP(hipGetLastError());
+    return MMPC_OK;
 }
 
 // one kernel launch for solver (not AUTO) on p.B instances
 int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
                   int barrier_rule) {
-    const mmpc_model_info& mi = h->info;
+    // every size below follows the horizon of the launch, p.N: the handle's, or N - n_pin of a pinned solve (the
+    // kernels lay their LDS and workspace out from p.N, and host and kernel must agree on one horizon)
+    const mmpc_model_info mi = with_horizon(h->info, p.N);
     const int64_t B = p.B;
-    const int N = mi.num_shooting_nodes;
+    const int N = p.N;
     // the barrier rule matters to the interior point alone (finite state bounds); Mehrotra's rule is built into the
     // 16-lane kernel for nonlinear solves -- anything else is refused, never run under the other rule
     const bool mehr = p.x_bounded != 0 && barrier_rule == MMPC_BARRIER_MEHROTRA;
@@ -1018,7 +1174,7 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
         const size_t lds = group_lds_bytes(mi, h->nq, bounded, xb);
         if (lds > kMaxGroupLds) return fail(MMPC_ERR_UNSUPPORTED, "group Riccati solver: stage data exceeds 160 KB LDS");
         LaneWork lw;
-        int rc = ensure_workspace(h, B, &lw);
+        int rc = ensure_workspace_bytes(h, solver_workspace_bytes(mi, h->nq, B) + kTailBytes, &lw.ws);
         if (rc) return rc;
         GroupWork gwk{lw.ws};
         dim3 grid(grid1d(B, kGroupsPerWave)), block(64);
@@ -1043,7 +1199,8 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
         if (h->opts.factor_fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 is a Riccati-solver option");
 #if MMPC_BUILTIN_MODELS
         // host-side shape checks: the kernel holds one condensed-Hessian row per lane
-        if (mi.model_id != MMPC_MODEL_TWO_LINK_ARM || N * TwoLinkArm::NU > 64)
+        // (supported or not by the handle's own N: a pinned solve runs the size class of its shorter horizon)
+        if (mi.model_id != MMPC_MODEL_TWO_LINK_ARM || h->info.num_shooting_nodes * TwoLinkArm::NU > 64)
             return fail(MMPC_ERR_UNSUPPORTED, "condensed solver needs the 2-link arm and N*nu <= 64");
         dim3 grid(static_cast<unsigned>(B)), block(64);
         if (bounded) {
@@ -1063,12 +1220,12 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
         if (rc) return rc;
         const TailPlan tp = tail_plan(h, p, bounded, h->cu_count);
         LaneWork lw;
-        rc = ensure_workspace_bytes(h, solver_workspace_bytes(h, B) + kTailBytes + tp.xb_ws_bytes, &lw.ws);
+        rc = ensure_workspace_bytes(h, solver_workspace_bytes(mi, h->nq, B) + kTailBytes + tp.xb_ws_bytes, &lw.ws);
         if (rc) return rc;
         dim3 grid(grid1d(B, 64)), block(64);
         SolveParams pl = p;
         if (tp.cap > 0) {   // the lane kernel hands instances still unconverged at iteration cap to a 16-lane launch
-            char* const tb = reinterpret_cast<char*>(lw.ws) + solver_workspace_bytes(h, B);
+            char* const tb = reinterpret_cast<char*>(lw.ws) + solver_workspace_bytes(mi, h->nq, B);
             pl.tail_cap = tp.cap;
             pl.tail_wave_max = tp.wave_max;
             pl.tail_slots = tp.slots;
@@ -1099,7 +1256,7 @@ int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded
                 pr.tail_lws_block = static_cast<int64_t>(lane_ws_doubles(nx, nu, h->nq, N, true)) * 64;
                 pr.tail_lws_ss = lane_stage_stride(nx, nu, true);
                 pr.tail_lws_zl = lane_zl_offset(nx, nu);
-                gwk.ws = lw.ws + (solver_workspace_bytes(h, B) + kTailBytes) / sizeof(double);
+                gwk.ws = lw.ws + (solver_workspace_bytes(mi, h->nq, B) + kTailBytes) / sizeof(double);
             }
             dim3 rgrid(static_cast<unsigned>((tp.slots + tp.gpw - 1) / tp.gpw)), rblock(64);
             rc = with_model(mi.model_id, [&](auto* m) {
@@ -1290,13 +1447,10 @@ int mmpc_reserve_workspace(mmpc_handle* h, int64_t B, uint64_t* bytes) {
     // not make a solve grow the workspace (a hipFree / hipMalloc inside a stream-ordered solve, or under a captured
     // hipGraph that still points at the old buffer)
     auto total = [&]() {
-        SolveParams p{};
-        p.B = B;
-        p.max_iter = h->opts.max_iter;
-        p.x_bounded = 1;
-        p.is_linear = h->info.is_linear;
         const int cu = h->cu_count > 0 ? h->cu_count : 256;
-        return solver_workspace_bytes(h, B) + kTailBytes + tail_plan(h, p, false, cu).xb_ws_bytes;
+        // every horizon 1..N a pinned solve may run, then the pinned solves' staging area (reserved whether or not
+        // pins are ever used, as the Mehrotra record is)
+        return solve_workspace_bytes_max(h, B, cu) + pin_staging_bytes(h->info, B);
     };
     if (bytes) *bytes = B == 0 ? 0 : total();
     if (B == 0) return MMPC_OK;
@@ -1344,6 +1498,28 @@ int mmpc_solve_batch_bounds(mmpc_handle* h, int64_t B, const double* x0, const d
                         kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out, bounds_stride);
 }
 
+int mmpc_solve_batch_pinned(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
+                            const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                            int64_t bounds_stride, const double* u_pin, int32_t n_pin, double* V_inout,
+                            int32_t* status, int32_t* iters, double* kkt_res, double* u0_out, void* stream) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (int rc = check_pins(h->info, u_pin, n_pin)) return rc;   // from the arguments alone, before any device call
+    if (n_pin == 0)
+        return mmpc_solve_batch_bounds(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride,
+                                       V_inout, status, iters, kkt_res, u0_out, stream);
+    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;
+    if (B == 0) return MMPC_OK;
+    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
+    int dev;
+    int rc = resolve_device(h, &dev);
+    if (rc) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    return launch_solve(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, V_inout, status, iters,
+                        kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out, bounds_stride, u_pin, n_pin);
+}
+
 int mmpc_host_alloc(uint64_t bytes, void** out) {
     if (!out) return fail(MMPC_ERR_INVALID_ARG, "null output pointer");
     *out = nullptr;
@@ -1373,7 +1549,17 @@ int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, co
                                  const double* traj, const double* weights, int64_t weights_stride,
                                  const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
                                  int32_t* status, int32_t* iters, double* kkt_res) {
+    return mmpc_solve_batch_host_pinned(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride,
+                                        nullptr, 0, V_inout, status, iters, kkt_res);
+}
+
+// the host entry of every solve: n_pin = 0 stages and launches exactly what mmpc_solve_batch_host_bounds always did
+int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev,
+                                 const double* traj, const double* weights, int64_t weights_stride,
+                                 const double* u_lb, const double* u_ub, int64_t bounds_stride, const double* u_pin,
+                                 int32_t n_pin, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (int rc = check_pins(h->info, u_pin, n_pin)) return rc;   // from the arguments alone
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
     if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;   // before the rows are scanned
     if (B == 0) return MMPC_OK;
@@ -1398,7 +1584,8 @@ int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, co
     // doubles: x0, u_prev, traj, weights, lb, ub, V, kkt ; ints: status, iters (as doubles' room)
     const size_t off_x0 = 0, off_up = off_x0 + B * nx, off_tr = off_up + B * nu, off_w = off_tr + B * N * nx;
     const size_t off_lb = off_w + nW, off_ub = off_lb + nB, off_V = off_ub + nB, off_kkt = off_V + B * NV;
-    const size_t off_st = off_kkt + B, off_it = off_st + (B + 1) / 2, total = off_it + (B + 1) / 2;
+    const size_t off_st = off_kkt + B, off_it = off_st + (B + 1) / 2, off_pin = off_it + (B + 1) / 2;
+    const size_t nP = static_cast<size_t>(B) * static_cast<size_t>(n_pin) * nu, total = off_pin + nP;   // pins last
     int dev;
     int rc = resolve_device(h, &dev);
     if (rc) return rc;
@@ -1415,11 +1602,12 @@ int mmpc_solve_batch_host_bounds(mmpc_handle* h, int64_t B, const double* x0, co
     if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
     if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
     MMPC_HIP(hipMemcpyAsync(d + off_V, V_inout, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_pin > 0) MMPC_HIP(hipMemcpyAsync(d + off_pin, u_pin, nP * sizeof(double), hipMemcpyHostToDevice, s));
     int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
     int32_t* dit = reinterpret_cast<int32_t*>(d + off_it);
     rc = launch_solve(h, B, d + off_x0, d + off_up, d + off_tr, d + off_w, weights_stride, u_lb ? d + off_lb : nullptr,
                       u_ub ? d + off_ub : nullptr, d + off_V, dst, dit, d + off_kkt, s, nullptr, nullptr,
-                      bounds_stride);
+                      bounds_stride, n_pin > 0 ? d + off_pin : nullptr, n_pin);
     if (rc) return rc;
     MMPC_HIP(hipMemcpyAsync(V_inout, d + off_V, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
     if (status) MMPC_HIP(hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1733,7 +1921,17 @@ int mmpc_multi_solve_batch_host_bounds(mmpc_multi* m, int64_t B, const double* x
                                        const double* traj, const double* weights, int64_t weights_stride,
                                        const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
                                        int32_t* status, int32_t* iters, double* kkt_res) {
+    return mmpc_multi_solve_batch_host_pinned(m, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub,
+                                              bounds_stride, nullptr, 0, V_inout, status, iters, kkt_res);
+}
+
+int mmpc_multi_solve_batch_host_pinned(mmpc_multi* m, int64_t B, const double* x0, const double* u_prev,
+                                       const double* traj, const double* weights, int64_t weights_stride,
+                                       const double* u_lb, const double* u_ub, int64_t bounds_stride,
+                                       const double* u_pin, int32_t n_pin, double* V_inout, int32_t* status,
+                                       int32_t* iters, double* kkt_res) {
     if (!m) return fail(MMPC_ERR_INVALID_ARG, "null multi-device handle");
+    if (int rc = check_pins(m->h[0]->info, u_pin, n_pin)) return rc;   // before any shard starts
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
     if (int rc = check_bounds_stride(m->h[0]->info, bounds_stride)) return rc;   // before any shard starts
     if (B == 0) return MMPC_OK;
@@ -1751,11 +1949,13 @@ int mmpc_multi_solve_batch_host_bounds(mmpc_multi* m, int64_t B, const double* x
         mmpc_shard(B, G, g, &first, &count);
         if (count == 0) return;
         // per-instance bounds: the shard's rows start at first * bounds_stride (stride 0: the shared row)
-        const int rc = mmpc_solve_batch_host_bounds(
+        // the pins of the shard: rows from first * n_pin * nu on
+        const int rc = mmpc_solve_batch_host_pinned(
             m->h[static_cast<size_t>(g)], count, x0 + first * nx, u_prev + first * nu, traj + first * N * nx,
             weights_stride ? weights + first * weights_stride : weights, weights_stride,
             u_lb ? u_lb + first * bounds_stride : nullptr, u_ub ? u_ub + first * bounds_stride : nullptr, bounds_stride,
-            V_inout + first * NV, status ? status + first : nullptr, iters ? iters + first : nullptr,
+            n_pin > 0 ? u_pin + first * n_pin * nu : nullptr, n_pin, V_inout + first * NV,
+            status ? status + first : nullptr, iters ? iters + first : nullptr,
             kkt_res ? kkt_res + first : nullptr);
         rcs[static_cast<size_t>(g)] = rc;
         if (rc) errs[static_cast<size_t>(g)] = g_last_error;   // thread-local: carried back to the caller

@@ -80,12 +80,20 @@ public:
     // (default), 1 = Mehrotra's predictor-corrector (mmpc_set_barrier_rule in include/mmpc.h: 16-lane solver, nonlinear
     // mode; a solve it does not cover then throws).  Additive: not part of the reference's interface.
     void set_barrier_rule(int rule);
+    // Committed controls, per instance (ModelControl::set_num_control_inputs_saved for every controller of the batch):
+    // from the first tick enqueued after a plan has been published, stage i < m of instance b is pinned to that
+    // instance's published control at index clamp(round((t - t_published) / step) + i, 0, N - 1) -- the plan
+    // published at enqueue time, which in the pipelined loop is the newest one a user of control_at_time can be
+    // applying.  The [B][m][nu] table is packed into the tick's staging slot and travels in its single H2D
+    // (mmpc_solve_batch_pinned).  m = 0 (default) pins nothing; m must be 0 .. N - 1.  Additive.
+    void set_num_control_inputs_saved(int m);
 
 private:
     struct Impl;
     std::unique_ptr<Impl> m;
     int64_t m_B;
     std::atomic<bool> m_shift{false};
+    std::atomic<int> m_num_control_inputs_saved{0};
     std::atomic<int64_t> m_ticks{0};
     std::atomic<bool> m_stop{true};
     std::thread m_thread;

@@ -62,6 +62,16 @@ public:
     // (default), 1 = Mehrotra's predictor-corrector (mmpc_set_barrier_rule in include/mmpc.h: 16-lane solver, nonlinear
     // mode; a solve it does not cover then throws).  Additive: not part of the reference's interface.
     void set_barrier_rule(int rule);
+    // Committed controls (delay compensation): the setter the reference's private m_num_control_inputs_saved
+    // (ModelControl.hpp:79) never got.  From the second calc_u on, the first m controls of the horizon are pinned to the
+    // controls the previous plan holds for those instants: stage i < m gets the previous plan's control at index
+    // clamp(round((t - t_prev) / step) + i, 0, N - 1), read under m_output_mutex as ModelControl.cpp:166 does; the
+    // first call pins nothing.  The solve then optimises only what can still be decided (mmpc_solve_batch_host_pinned).
+    // Departure from the reference's stub (ModelControl.cpp:165-171), which is dead: it copies index for index (no
+    // shift by the elapsed time) into lbx / ubx, and the next calc_u overwrites those with u_min / u_max (:150-153)
+    // before solving.  m = 0 (the default) is the reference's behaviour; m must be 0 .. N - 1; linear-mode models
+    // throw at the first pinned solve.  Additive: not part of the reference's interface.
+    void set_num_control_inputs_saved(int m);
 
     // ---- build extensions (not in the reference) ----
     // solver status of the last calc_u (the reference ignores IPOPT's status, ModelControl.cpp:159-161)
@@ -102,6 +112,8 @@ private:
     std::mutex m_output_mutex;
     std::mutex m_control_limits_mutex;
     std::mutex m_weights_mutex;
+
+    std::atomic<int> m_num_control_inputs_saved{0};  // ModelControl.hpp:79 (there an int without a setter)
 
     int m_last_status = -1;
     int m_last_iters = 0;

@@ -35,7 +35,9 @@ struct BatchModelControl::Impl {
     int64_t B = 0;
     // per-slot input block (device and pinned host): x0 [B nx] | u_prev [B nu] | traj [B N nx] | Q R Rm | lb | ub |
     // lb table [B nu] | ub table [B nu] (per-instance limits: uploaded, in the same single H2D, only while in use)
+    // | committed controls [B m nu], packed right after whatever else the tick uploads (no gap, one H2D)
     size_t off_up = 0, off_tr = 0, off_w = 0, off_lb = 0, off_ub = 0, off_lbt = 0, off_ubt = 0, in_doubles = 0;
+    size_t slot_doubles = 0;  // in_doubles + the largest pin table, B (N - 1) nu
     double* d_in[2] = {nullptr, nullptr};
     double* h_in[2] = {nullptr, nullptr};
     bool bounded[2] = {false, false};
@@ -97,14 +99,15 @@ BatchModelControl::BatchModelControl(std::string model_name, int64_t B, std::vec
     m->off_lbt = m->off_ub + nu;
     m->off_ubt = m->off_lbt + b * nu;
     m->in_doubles = m->off_ubt + b * nu;
+    m->slot_doubles = m->in_doubles + b * (N > 1 ? N - 1 : 0) * nu;
     HIPC(hipStreamCreateWithFlags(&m->compute, hipStreamNonBlocking));
     HIPC(hipStreamCreateWithFlags(&m->copy, hipStreamNonBlocking));
     HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_V), b * NV * sizeof(double)));
     HIPC(hipMemset(m->d_V, 0, b * NV * sizeof(double)));  // v_init = 0 (ModelControl.cpp:29-50)
     HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_tmp), b * NV * sizeof(double)));
     for (int s = 0; s < 2; ++s) {
-        HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_in[s]), m->in_doubles * sizeof(double)));
-        HIPC(hipHostMalloc(reinterpret_cast<void**>(&m->h_in[s]), m->in_doubles * sizeof(double), hipHostMallocDefault));
+        HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_in[s]), m->slot_doubles * sizeof(double)));
+        HIPC(hipHostMalloc(reinterpret_cast<void**>(&m->h_in[s]), m->slot_doubles * sizeof(double), hipHostMallocDefault));
         HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_Vout[s]), b * NV * sizeof(double)));
         HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_st[s]), b * sizeof(int32_t)));
         HIPC(hipMalloc(reinterpret_cast<void**>(&m->d_it[s]), b * sizeof(int32_t)));
@@ -186,7 +189,27 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
     I.bounded[slot] = finite;
     double* d = I.d_in[slot];
     // one H2D per tick: the per-instance tables lie at the end of the slot and travel only while they are in use
-    const size_t up_doubles = per_instance ? I.in_doubles : I.off_lbt;
+    size_t up_doubles = per_instance ? I.in_doubles : I.off_lbt;
+    // committed controls: per instance, the published plan's controls for the first n_pin instants of this horizon
+    // (index clamp(round((t - t_published) / step) + i, 0, N - 1), the warm-start shift's rule), packed after the
+    // rest of the upload; nothing is pinned before a plan has been published
+    const int want_pin = m_num_control_inputs_saved.load();
+    int32_t n_pin = 0;
+    const size_t off_pin = up_doubles;
+    if (want_pin > 0) {
+        std::lock_guard<std::mutex> lg(m_output_mutex);
+        if (m_ticks > 0) {
+            n_pin = want_pin;
+            const int64_t k0 = std::llround((time.as_seconds() - m_out_time.as_seconds()) / I.step);
+            for (size_t i = 0; i < b; ++i)
+                for (int s = 0; s < n_pin; ++s) {
+                    const size_t k = static_cast<size_t>(std::min<int64_t>(I.N - 1, std::max<int64_t>(0, k0 + s)));
+                    const double* u = m_out_V.data() + i * NV + k * (nx + nu) + nx;
+                    std::copy(u, u + nu, in + off_pin + (i * n_pin + s) * nu);
+                }
+            up_doubles += b * n_pin * nu;
+        }
+    }
     HIPC(hipMemcpyAsync(d, in, up_doubles * sizeof(double), hipMemcpyHostToDevice, I.copy));
     HIPC(hipEventRecord(I.h2d_done[slot], I.copy));
     HIPC(hipStreamWaitEvent(I.compute, I.h2d_done[slot], 0));
@@ -204,11 +227,18 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
     I.have_prev = true;
     I.prev_time = time;
     const size_t olb = per_instance ? I.off_lbt : I.off_lb, oub = per_instance ? I.off_ubt : I.off_ub;
-    I.check(I.lib->solve_batch_bounds(I.h, I.B, d, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
-                                      finite ? d + olb : nullptr, finite ? d + oub : nullptr,
-                                      per_instance ? static_cast<int64_t>(nu) : 0, I.d_V, I.d_st[slot], I.d_it[slot],
-                                      nullptr, nullptr, I.compute),
-            "mmpc_solve_batch_bounds");
+    if (n_pin == 0)
+        I.check(I.lib->solve_batch_bounds(I.h, I.B, d, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
+                                          finite ? d + olb : nullptr, finite ? d + oub : nullptr,
+                                          per_instance ? static_cast<int64_t>(nu) : 0, I.d_V, I.d_st[slot],
+                                          I.d_it[slot], nullptr, nullptr, I.compute),
+                "mmpc_solve_batch_bounds");
+    else
+        I.check(I.lib->solve_batch_pinned(I.h, I.B, d, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
+                                          finite ? d + olb : nullptr, finite ? d + oub : nullptr,
+                                          per_instance ? static_cast<int64_t>(nu) : 0, d + off_pin, n_pin, I.d_V,
+                                          I.d_st[slot], I.d_it[slot], nullptr, nullptr, I.compute),
+                "mmpc_solve_batch_pinned");
     // the next solve updates d_V in place: download from a per-slot copy
     HIPC(hipMemcpyAsync(I.d_Vout[slot], I.d_V, b * NV * sizeof(double), hipMemcpyDeviceToDevice, I.compute));
     HIPC(hipEventRecord(I.solved[slot], I.compute));
@@ -400,6 +430,12 @@ void BatchModelControl::update_control_limits(int64_t b, std::vector<double> u_m
     }
     std::copy(u_min.begin(), u_min.end(), m_u_min_table.begin() + static_cast<size_t>(b) * nu);
     std::copy(u_max.begin(), u_max.end(), m_u_max_table.begin() + static_cast<size_t>(b) * nu);
+}
+
+void BatchModelControl::set_num_control_inputs_saved(int m_pin) {
+    if (m_pin < 0 || m_pin > m->N - 1)
+        throw std::invalid_argument("set_num_control_inputs_saved: m must be 0 .. num_shooting_nodes - 1");
+    m_num_control_inputs_saved = m_pin;
 }
 
 void BatchModelControl::set_barrier_rule(int rule) {

@@ -5,7 +5,9 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -76,12 +78,33 @@ void ModelControl::calc_u(mahi::util::Time control_time, const std::vector<doubl
     }
     int32_t st = -1, it = 0;
     double kkt = 0.0;
+    // committed controls: the previous plan's controls for the first m instants of this horizon (none on the first call)
+    std::vector<double> pin;
+    if (const int m = m_num_control_inputs_saved.load()) {
+        std::lock_guard<std::mutex> lg(m_output_mutex);  // ModelControl.cpp:166
+        if (!control_results.empty()) {
+            const double dt = control_time.as_seconds() - control_results[0].time.as_seconds();
+            const long long k0 = std::llround(dt / model_parameters.step_size.as_seconds());
+            for (int i = 0; i < m; ++i) {
+                const long long k = std::min<long long>(static_cast<long long>(N) - 1, std::max<long long>(0, k0 + i));
+                const std::vector<double>& u = control_results[static_cast<size_t>(k)].u;
+                pin.insert(pin.end(), u.begin(), u.end());
+            }
+        }
+    }
     // linear mode: the per-step linearisation at (state, control) of ModelControl.cpp:125-135 happens on the
     // device inside the solve; x_0 is pinned to `state` (ModelControl.cpp:144-145)
-    m_backend->check(m_backend->solve_batch_host(m_handle, 1, state.data(), control.data(), traj.data(), w.data(), 0,
-                                lb.size() == nu ? lb.data() : nullptr, ub.size() == nu ? ub.data() : nullptr,
-                                m_V.data(), &st, &it, &kkt),
-          "mmpc_solve_batch_host");
+    if (pin.empty())
+        m_backend->check(m_backend->solve_batch_host(m_handle, 1, state.data(), control.data(), traj.data(), w.data(), 0,
+                                    lb.size() == nu ? lb.data() : nullptr, ub.size() == nu ? ub.data() : nullptr,
+                                    m_V.data(), &st, &it, &kkt),
+              "mmpc_solve_batch_host");
+    else
+        m_backend->check(m_backend->solve_batch_host_pinned(
+                             m_handle, 1, state.data(), control.data(), traj.data(), w.data(), 0,
+                             lb.size() == nu ? lb.data() : nullptr, ub.size() == nu ? ub.data() : nullptr, 0, pin.data(),
+                             static_cast<int32_t>(pin.size() / nu), m_V.data(), &st, &it, &kkt),
+                         "mmpc_solve_batch_host_pinned");
     m_last_status = st;
     m_last_iters = it;
     m_last_kkt = kkt;
@@ -234,6 +257,12 @@ void ModelControl::update_control_limits(std::vector<double> u_min, std::vector<
     std::lock_guard<std::mutex> lg(m_control_limits_mutex);
     model_parameters.u_min = u_min;
     model_parameters.u_max = u_max;
+}
+
+void ModelControl::set_num_control_inputs_saved(int m) {
+    if (m < 0 || m > model_parameters.num_shooting_nodes - 1)
+        throw std::invalid_argument("set_num_control_inputs_saved: m must be 0 .. num_shooting_nodes - 1");
+    m_num_control_inputs_saved = m;
 }
 
 void ModelControl::set_barrier_rule(int rule) {

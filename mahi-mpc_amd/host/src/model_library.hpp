@@ -29,6 +29,9 @@ struct ModelLibrary {
     // per-instance control limits (bounds_stride): the batched mirror of update_control_limits per controller
     decltype(&mmpc_solve_batch_bounds) solve_batch_bounds = &mmpc_solve_batch_bounds;
     decltype(&mmpc_solve_batch_host_bounds) solve_batch_host_bounds = &mmpc_solve_batch_host_bounds;
+    // committed controls (u_pin, n_pin): the mirror of set_num_control_inputs_saved
+    decltype(&mmpc_solve_batch_pinned) solve_batch_pinned = &mmpc_solve_batch_pinned;
+    decltype(&mmpc_solve_batch_host_pinned) solve_batch_host_pinned = &mmpc_solve_batch_host_pinned;
     decltype(&mmpc_reserve_workspace) reserve_workspace = &mmpc_reserve_workspace;
     decltype(&mmpc_set_barrier_rule) set_barrier_rule = &mmpc_set_barrier_rule;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
@@ -76,6 +79,8 @@ struct ModelLibrary {
         b->bind(b->solve_batch, "mmpc_solve_batch");
         b->bind(b->solve_batch_bounds, "mmpc_solve_batch_bounds");
         b->bind(b->solve_batch_host_bounds, "mmpc_solve_batch_host_bounds");
+        b->bind(b->solve_batch_pinned, "mmpc_solve_batch_pinned");
+        b->bind(b->solve_batch_host_pinned, "mmpc_solve_batch_host_pinned");
         b->bind(b->reserve_workspace, "mmpc_reserve_workspace");
         b->bind(b->set_barrier_rule, "mmpc_set_barrier_rule");
         b->bind(b->last_error, "mmpc_last_error");

@@ -116,6 +116,11 @@ def lib(path: str | None = None):
         L.mmpc_multi_solve_batch_host_bounds.argtypes = L.mmpc_solve_batch_host_bounds.argtypes
         L.mmpc_multi_solve_batch_rccl_bounds.argtypes = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64]
                                                          + [_vp] * 5)
+        # committed controls: the *_bounds signatures plus (u_pin, n_pin) after bounds_stride
+        _pin = [_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int32]
+        L.mmpc_solve_batch_pinned.argtypes = _pin + [_vp] * 6
+        L.mmpc_solve_batch_host_pinned.argtypes = _pin + [_vp] * 4
+        L.mmpc_multi_solve_batch_host_pinned.argtypes = _pin + [_vp] * 4
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -271,6 +276,20 @@ def _host_bounds(u_lb, u_ub, B, nu):
     return rows(lb), rows(ub), nu
 
 
+def _host_pins(u_pin, B, nu, N):
+    """(pins, n_pin) of host committed controls: None pins nothing; otherwise a [B, m, nu] array, m from its shape
+    (0 <= m <= N - 1).  A wrong shape raises ValueError before the library is called."""
+    if u_pin is None:
+        return None, 0
+    a = np.asarray(u_pin, dtype=np.float64)
+    if a.ndim != 3 or a.shape[0] != B or a.shape[2] != nu:
+        raise ValueError(f"u_pin of shape {a.shape}: expected ({B}, m, {nu})")
+    m = a.shape[1]
+    if m > N - 1:
+        raise ValueError(f"u_pin pins {m} controls: at most N - 1 = {N - 1}")
+    return (np.ascontiguousarray(a), m) if m else (None, 0)
+
+
 class Solver:
     """One loaded model (the reference's ModelControl without the thread/bookkeeping)."""
 
@@ -339,12 +358,19 @@ class Solver:
 
     # ---- device-pointer API (torch tensors on the GPU or raw addresses) ----
     def solve_batch(self, B, x0, u_prev, traj, weights, V, status=None, iters=None, kkt=None,
-                    weights_stride=0, u_lb=None, u_ub=None, stream=None, u0=None, bounds_stride=0):
+                    weights_stride=0, u_lb=None, u_ub=None, stream=None, u0=None, bounds_stride=0, u_pin=None,
+                    n_pin=0):
         """Device-pointer solve (stream-ordered).  u0: optional [B][nu] output of u_0* (mmpc_solve_batch_u0);
         u0 / status / iters may be HostBuffer views (results stored by the kernel straight into host memory).
         bounds_stride: 0 = u_lb / u_ub are [nu], shared; >= nu = instance b's row starts at b * bounds_stride
-        (mmpc_solve_batch_bounds)."""
-        if bounds_stride:
+        (mmpc_solve_batch_bounds).  u_pin, n_pin: committed controls, device [B][n_pin][nu] -- the first n_pin
+        controls of every instance are fixed to them (mmpc_solve_batch_pinned; n_pin = 0 pins nothing)."""
+        if n_pin:
+            self._check(self._L.mmpc_solve_batch_pinned(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                        weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                        _ptr(u_pin), int(n_pin), _ptr(V), _ptr(status), _ptr(iters),
+                                                        _ptr(kkt), _ptr(u0), stream))
+        elif bounds_stride:
             self._check(self._L.mmpc_solve_batch_bounds(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
                                                         weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
                                                         _ptr(V), _ptr(status), _ptr(iters), _ptr(kkt), _ptr(u0),
@@ -380,10 +406,13 @@ class Solver:
         self._check(self._L.mmpc_linearize_batch(self._h, B, _ptr(x), _ptr(u), _ptr(A), _ptr(Bm), _ptr(xdot), stream))
 
     # ---- host (numpy) API, synchronous ----
-    def solve_batch_host(self, x0, u_prev, traj, weights, V=None, u_lb=None, u_ub=None):
+    def solve_batch_host(self, x0, u_prev, traj, weights, V=None, u_lb=None, u_ub=None, u_pin=None):
+        """u_pin: committed controls [B, m, nu] (m from the shape): the first m controls of every instance are
+        fixed to them (mmpc_solve_batch_host_pinned); None pins nothing."""
         nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
         x0 = _f64(x0, (-1, nx))
         B = x0.shape[0]
+        pin, m = _host_pins(u_pin, B, nu, N)
         u_prev = _f64(u_prev, (B, nu))
         traj = _f64(traj, (B, N, nx))
         weights = _f64(weights)
@@ -393,6 +422,11 @@ class Solver:
         it = np.zeros(B, np.int32)
         kkt = np.zeros(B)
         lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)   # [nu] shared, or [B, nu] per instance
+        if m:
+            self._check(self._L.mmpc_solve_batch_host_pinned(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj),
+                                                             _ptr(weights), ws, _ptr(lb), _ptr(ub), bs, _ptr(pin), m,
+                                                             _ptr(V), _ptr(st), _ptr(it), _ptr(kkt)))
+            return dict(V=V, status=st, iters=it, kkt=kkt)
         self._check(self._L.mmpc_solve_batch_host_bounds(self._h, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
                                                          ws, _ptr(lb), _ptr(ub), bs, _ptr(V), _ptr(st), _ptr(it),
                                                          _ptr(kkt)))
@@ -473,15 +507,22 @@ class MultiSolver:
         _check(self._L.mmpc_multi_num_devices(self._m, C.byref(n)), self._L)
         return n.value
 
-    def solve_batch_host(self, x0, u_prev, traj, weights, V=None, u_lb=None, u_ub=None):
+    def solve_batch_host(self, x0, u_prev, traj, weights, V=None, u_lb=None, u_ub=None, u_pin=None):
+        """u_pin: committed controls [B, m, nu], sharded with the instances (mmpc_multi_solve_batch_host_pinned)"""
         nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
         x0 = _f64(x0, (-1, nx))
         B = x0.shape[0]
+        pin, m = _host_pins(u_pin, B, nu, N)
         u_prev, traj, weights = _f64(u_prev, (B, nu)), _f64(traj, (B, N, nx)), _f64(weights)
         ws = 0 if weights.ndim == 1 else weights.shape[-1]
         V = np.zeros((B, NV)) if V is None else _f64(V, (B, NV)).copy()
         st, it, kkt = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
         lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)   # [nu] shared, or [B, nu] per instance
+        if m:
+            _check(self._L.mmpc_multi_solve_batch_host_pinned(self._m, B, _ptr(x0), _ptr(u_prev), _ptr(traj),
+                                                              _ptr(weights), ws, _ptr(lb), _ptr(ub), bs, _ptr(pin), m,
+                                                              _ptr(V), _ptr(st), _ptr(it), _ptr(kkt)), self._L)
+            return dict(V=V, status=st, iters=it, kkt=kkt)
         _check(self._L.mmpc_multi_solve_batch_host_bounds(self._m, B, _ptr(x0), _ptr(u_prev), _ptr(traj), _ptr(weights),
                                                           ws, _ptr(lb), _ptr(ub), bs, _ptr(V), _ptr(st), _ptr(it),
                                                           _ptr(kkt)), self._L)
