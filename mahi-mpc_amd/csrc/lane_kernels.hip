@@ -18,57 +18,35 @@
 
 namespace mmpc {
 namespace {
-template <class Model, class FT>
-void launch_lane(bool bounded, bool xb, bool exact, dim3 grid, dim3 block, hipStream_t stream, const SolveParams& p,
-                 LaneWork lw) {
-    if (p.b_stride != 0 && (xb || bounded)) {   // per-instance control bounds: the IB instantiations
-        if constexpr (HasHess<Model>::value && std::is_same<FT, double>::value) {
-            if (exact) {
-                if (xb) sqp_lane_kernel<Model, double, false, true, true, true><<<grid, block, 0, stream>>>(p, lw);
-                else sqp_lane_kernel<Model, double, true, false, true, true><<<grid, block, 0, stream>>>(p, lw);
-                return;
-            }
-        }
-        if (xb) sqp_lane_kernel<Model, FT, false, true, false, true><<<grid, block, 0, stream>>>(p, lw);
-        else sqp_lane_kernel<Model, FT, true, false, false, true><<<grid, block, 0, stream>>>(p, lw);
-        return;
-    }
-    if constexpr (HasHess<Model>::value && std::is_same<FT, double>::value) {
-        if (exact) {
-            if (xb) sqp_lane_kernel<Model, double, false, true, true><<<grid, block, 0, stream>>>(p, lw);
-            else if (bounded) sqp_lane_kernel<Model, double, true, false, true><<<grid, block, 0, stream>>>(p, lw);
-            else sqp_lane_kernel<Model, double, false, false, true><<<grid, block, 0, stream>>>(p, lw);
-            return;
-        }
-    }
-    if (xb) sqp_lane_kernel<Model, FT, false, true><<<grid, block, 0, stream>>>(p, lw);
-    else if (bounded) sqp_lane_kernel<Model, FT, true><<<grid, block, 0, stream>>>(p, lw);
-    else sqp_lane_kernel<Model, FT, false><<<grid, block, 0, stream>>>(p, lw);
+// the lane kernels of a model: the monotone barrier rule only, the exact Hessian for models with second derivatives
+// (fp64 factor: a canonical key is never fp32 and exact); per-instance bounds (IB) on the bounded instantiations only
+template <class Model>
+constexpr bool has_lane_kernel(const KernelVariant& v) {
+    return canonical(v) && !v.mehr && (!v.exact || HasHess<Model>::value);
 }
 template <class Model>
-void launch_model(bool fp32, bool bounded, bool xb, bool exact, dim3 grid, dim3 block, hipStream_t stream,
-                  const SolveParams& p, LaneWork lw) {
-    if (fp32) launch_lane<Model, float>(bounded, xb, false, grid, block, stream, p, lw);
-    else launch_lane<Model, double>(bounded, xb, exact, grid, block, stream, p, lw);
+int launch_model(const KernelVariant& v, dim3 grid, dim3 block, hipStream_t stream, const SolveParams& p,
+                 const LaneWork& lw) {
+    return with_variant(v, [&](auto sv) {
+        constexpr KernelVariant V = decltype(sv)::value;
+        if constexpr (has_lane_kernel<Model>(V)) {
+            using FT = std::conditional_t<V.fp32, float, double>;
+            sqp_lane_kernel<Model, FT, V.ub, V.xb, V.exact, V.instb><<<grid, block, 0, stream>>>(p, lw);
+            return 0;
+        } else {
+            return -2;
+        }
+    });
 }
 }  // namespace
 
-int launch_lane_kernels(int model_id, bool fp32, bool bounded, bool xb, bool exact, dim3 grid, dim3 block,
-                        hipStream_t stream, const SolveParams& p, const LaneWork& lw) {
+int launch_lane_kernels(int model_id, const KernelVariant& v, dim3 grid, dim3 block, hipStream_t stream,
+                        const SolveParams& p, const LaneWork& lw) {
 #if MMPC_LANE_BUILTIN_MODELS
-    if (model_id == MMPC_MODEL_TWO_LINK_ARM) {
-        launch_model<TwoLinkArm>(fp32, bounded, xb, exact, grid, block, stream, p, lw);
-        return 0;
-    }
-    if (model_id == MMPC_MODEL_EXO_ARM) {
-        launch_model<ExoArm>(fp32, bounded, xb, exact, grid, block, stream, p, lw);
-        return 0;
-    }
+    if (model_id == MMPC_MODEL_TWO_LINK_ARM) return launch_model<TwoLinkArm>(v, grid, block, stream, p, lw);
+    if (model_id == MMPC_MODEL_EXO_ARM) return launch_model<ExoArm>(v, grid, block, stream, p, lw);
 #else
-    if (model_id == MMPC_MODEL_USER) {
-        launch_model<UserModel>(fp32, bounded, xb, exact, grid, block, stream, p, lw);
-        return 0;
-    }
+    if (model_id == MMPC_MODEL_USER) return launch_model<UserModel>(v, grid, block, stream, p, lw);
 #endif
     return -1;
 }

@@ -716,33 +716,37 @@ mmpc_model_info with_horizon(const mmpc_model_info& mi, int N) {
     return r;
 }
 
-size_t workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B, bool xb = true) {
-    const int64_t blocks = (B + 63) / 64;
-    return static_cast<size_t>(lane_ws_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, xb)) * 64u *
-           static_cast<size_t>(blocks) * sizeof(double);
+// Sizes by key (kernel_variant.h): the kernels stride their LDS and workspace by their own template flags (sqp_group.h
+// group_lds_doubles / group_ws_doubles, sqp_lane.h lane_ws_doubles), and these are the host's only calls of those
+// functions, each flag taken from the key's member of the same meaning.
+// per-instance doubles of the 16-lane kernel's workspace (the host never counts on the on-chip W record)
+int group_ws_doubles(const mmpc_model_info& mi, const KernelVariant& v) {
+    return mmpc::group_ws_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, v.ub, v.xb, false, v.mehr);
 }
-
-// the largest variant's: bounded, or xb under Mehrotra's rule -- whichever barrier rule the handle has now, so that
-// mmpc_set_barrier_rule after a reservation never makes a solve grow the workspace
-size_t group_workspace_bytes(const mmpc_model_info& mi, int64_t B) {
-    const int nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes;
-    const int per = std::max(group_ws_doubles(nx, nu, N, true, false),
-                             group_ws_doubles(nx, nu, N, false, true, false, true));
-    return static_cast<size_t>(per) * static_cast<size_t>(B) * sizeof(double);
+int lane_ws_doubles(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
+    return mmpc::lane_ws_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.xb);
 }
-size_t group_lds_bytes(const mmpc_model_info& mi, int nq, bool bounded = true, bool xb = false) {
-    return static_cast<size_t>(group_lds_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, bounded && !xb,
-                                                 mi.is_linear != 0, xb)) * kGroupsPerWave *
-           sizeof(double);
+// LDS of one instance group of the 16-lane kernel, and of a full workgroup of kGroupsPerWave of them
+size_t group_lds_instance_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
+    return static_cast<size_t>(mmpc::group_lds_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.ub,
+                                                       mi.is_linear != 0, v.xb)) * sizeof(double);
+}
+size_t group_lds_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
+    return group_lds_instance_bytes(mi, nq, v) * kGroupsPerWave;
 }
 constexpr size_t kMaxGroupLds = 160 * 1024;  // gfx950: 160 KB of LDS per workgroup (attribute raised above 64 KB)
 
-template <class K>
-int set_dynamic_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return MMPC_OK;
-    MMPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 static_cast<int>(bytes)));
-    return MMPC_OK;
+// Solver workspace of B instances, whichever kernel and variant runs them: the lane kernels' with the interior point's
+// stage fields, or the largest of the 16-lane kernels' -- control bounds, or state bounds under Mehrotra's rule, counted
+// whichever barrier rule the handle has now, so that mmpc_set_barrier_rule after a reservation never makes a solve
+// grow it
+size_t solver_workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B) {
+    const size_t lane = static_cast<size_t>(lane_ws_doubles(mi, nq, kVariantXb)) * 64u *
+                        static_cast<size_t>((B + 63) / 64) * sizeof(double);
+    const size_t group = static_cast<size_t>(std::max(group_ws_doubles(mi, kVariantUb),
+                                                      group_ws_doubles(mi, kVariantXbMehrotra))) *
+                         static_cast<size_t>(B) * sizeof(double);
+    return (std::max(lane, group) + 255) / 256 * 256;
 }
 
 // opts.kkt_solver, or the AUTO choice before state bounds are considered
@@ -756,7 +760,7 @@ int resolve_kkt_solver_base(const mmpc_handle* h, int64_t B) {
     const int N = mi.num_shooting_nodes;
     // LDS of the layout launch_kernel will use: the interior-point fields with state bounds, else the bounded
     // solves' hold targets (the larger of the two control-bound variants)
-    const size_t glds = group_lds_bytes(mi, h->nq, true, h->x_bounded);
+    const size_t glds = group_lds_bytes(mi, h->nq, h->x_bounded ? kVariantXb : kVariantUb);
     if (mi.model_id == MMPC_MODEL_USER) {  // SX-generated dynamics: no condensed kernel (it is 2-link specific)
         if (glds <= kMaxGroupLds / 2 && B * static_cast<int64_t>(N) <= 1000000) return MMPC_KKT_RICCATI_GROUP;
         return MMPC_KKT_RICCATI;
@@ -777,7 +781,7 @@ int resolve_kkt_solver(const mmpc_handle* h, int64_t B) {
     const int s = resolve_kkt_solver_base(h, B);
     // state bounds (interior-point variant): the Riccati solvers only; the group kernel when its LDS layout fits
     if (h->x_bounded && h->opts.kkt_solver == MMPC_KKT_AUTO && s == MMPC_KKT_CONDENSED)
-        return group_lds_bytes(h->info, h->nq, true, true) <= kMaxGroupLds ? MMPC_KKT_RICCATI_GROUP : MMPC_KKT_RICCATI;
+        return group_lds_bytes(h->info, h->nq, kVariantXb) <= kMaxGroupLds ? MMPC_KKT_RICCATI_GROUP : MMPC_KKT_RICCATI;
     return s;
 }
 
@@ -828,83 +832,34 @@ int resolve_hessian(const mmpc_handle* h, int solver, bool u_bounded) {
     return group_ok && dflt && !u_bounded && !h->x_bounded ? MMPC_HESSIAN_EXACT : MMPC_HESSIAN_GAUSS_NEWTON;
 }
 
-template <class Model, bool BOUNDED, bool XB = false, bool EXACT = false>
-int launch_group(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
-    int rc = set_dynamic_lds(sqp_group_kernel<Model, BOUNDED, XB, EXACT>, lds);
-    if (rc) return rc;
-    sqp_group_kernel<Model, BOUNDED, XB, EXACT><<<grid, block, lds, stream>>>(p, gwk);
-    return MMPC_OK;
-}
-// the bounded 16-lane kernels with per-instance control bounds (SolveParams::b_stride != 0)
-template <class Model, bool BOUNDED, bool XB, bool EXACT, bool MEHR>
-int launch_group_instb(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p, GroupWork gwk) {
-    int rc = set_dynamic_lds(sqp_group_instb_kernel<Model, BOUNDED, XB, EXACT, MEHR>, lds);
-    if (rc) return rc;
-    sqp_group_instb_kernel<Model, BOUNDED, XB, EXACT, MEHR><<<grid, block, lds, stream>>>(p, gwk);
-    return MMPC_OK;
-}
-// the 16-lane kernel of model M for (ub: control bounds only, xb: state bounds, exact Hessian); `what` names the launch
-// in an error text.  The built-in 2-link arm's kernels live in the units of group_launch.h.
+// the 16-lane kernels this unit instantiates for model M: every canonical fp64 variant, the exact Hessian for
+// exact_capable models, Mehrotra's rule on the lane-distributed path (nx + nu < 16).  None for the built-in 2-link arm:
+// its kernels live in the units of group_launch.h.
 template <class M>
-int dispatch_group(bool ub, bool xb, bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-                   const SolveParams& p, GroupWork gwk, const char* what) {
-    if constexpr (std::is_same<M, TwoLinkArm>::value) {
-        const hipError_t e = (ub || xb) ? launch_group_two_link_bounded(xb, exact, grid, block, lds, stream, p, gwk)
-                                        : launch_group_two_link(exact, grid, block, lds, stream, p, gwk);
-        return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    } else {
-        if (p.b_stride != 0 && (ub || xb)) {   // per-instance control bounds
-            if constexpr (exact_capable<M>()) {
-                if (exact)
-                    return xb ? launch_group_instb<M, false, true, true, false>(grid, block, lds, stream, p, gwk)
-                              : launch_group_instb<M, true, false, true, false>(grid, block, lds, stream, p, gwk);
-            }
-            return xb ? launch_group_instb<M, false, true, false, false>(grid, block, lds, stream, p, gwk)
-                      : launch_group_instb<M, true, false, false, false>(grid, block, lds, stream, p, gwk);
-        }
-        if constexpr (exact_capable<M>()) {
-            if (exact)
-                return xb   ? launch_group<M, false, true, true>(grid, block, lds, stream, p, gwk)
-                       : ub ? launch_group<M, true, false, true>(grid, block, lds, stream, p, gwk)
-                            : launch_group<M, false, false, true>(grid, block, lds, stream, p, gwk);
-        }
-        return xb   ? launch_group<M, false, true>(grid, block, lds, stream, p, gwk)
-               : ub ? launch_group<M, true>(grid, block, lds, stream, p, gwk)
-                    : launch_group<M, false>(grid, block, lds, stream, p, gwk);
-    }
+constexpr bool has_group_kernel(const KernelVariant& v) {
+    return !std::is_same<M, TwoLinkArm>::value && canonical(v) && !v.fp32 && (!v.exact || exact_capable<M>()) &&
+           (!v.mehr || M::NX + M::NU < kGroupLanes);
 }
-
-// the interior point under Mehrotra's predictor-corrector rule (sqp_group_mehrotra_kernel): state-bounded solves of the
-// models on the lane-distributed path (nx + nu < 16)
+// launches the 16-lane kernel of model M for the key v; `what` names the launch in an error text
 template <class M>
-int dispatch_group_mehrotra(bool exact, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveParams& p,
-                            GroupWork gwk) {
-    if constexpr (std::is_same<M, TwoLinkArm>::value) {
-        const hipError_t e = launch_group_two_link_mehrotra(exact, grid, block, lds, stream, p, gwk);
-        return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string("group kernel launch: ") + hipGetErrorString(e));
-    } else if constexpr (M::NX + M::NU < kGroupLanes) {
-        if (p.b_stride != 0) {   // per-instance control bounds
-            if constexpr (exact_capable<M>()) {
-                if (exact) return launch_group_instb<M, false, true, true, true>(grid, block, lds, stream, p, gwk);
-            }
-            return launch_group_instb<M, false, true, false, true>(grid, block, lds, stream, p, gwk);
-        }
-        if constexpr (exact_capable<M>()) {
-            if (exact) {
-                const int rc = set_dynamic_lds(sqp_group_mehrotra_kernel<M, true>, lds);
-                if (rc) return rc;
-                sqp_group_mehrotra_kernel<M, true><<<grid, block, lds, stream>>>(p, gwk);
-                return MMPC_OK;
-            }
-        }
-        const int rc = set_dynamic_lds(sqp_group_mehrotra_kernel<M, false>, lds);
-        if (rc) return rc;
-        sqp_group_mehrotra_kernel<M, false><<<grid, block, lds, stream>>>(p, gwk);
-        return MMPC_OK;
-    } else {
+int launch_group_of(const KernelVariant& v, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                    const SolveParams& p, const GroupWork& gwk, const char* what) {
+    if (v.mehr && M::NX + M::NU >= kGroupLanes)
         return fail(MMPC_ERR_UNSUPPORTED, "barrier rule MEHROTRA: the 16-lane solver runs it for models with "
                                           "nx + nu < 16 only");
+    hipError_t e;
+    if constexpr (std::is_same<M, TwoLinkArm>::value) {
+        e = (v.ub || v.xb) ? launch_group_two_link_bounded(v, grid, block, lds, stream, p, gwk)
+                           : launch_group_two_link(v, grid, block, lds, stream, p, gwk);
+    } else {
+        e = with_variant(v, [&](auto sv) {
+            if constexpr (has_group_kernel<M>(decltype(sv)::value))
+                return launch_group_kernel<M>(sv, grid, block, lds, stream, p, gwk);
+            else
+                return hipErrorInvalidValue;   // a key with no kernel (resolve_hessian never asks for one)
+        });
     }
+    return e == hipSuccess ? MMPC_OK : fail(MMPC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 // Riccati workspace (sqp_lane.h / sqp_group.h layouts), grown on demand.  Growth is synchronous:
@@ -929,12 +884,6 @@ int ensure_workspace_bytes(mmpc_handle* h, size_t bytes, double** out) {
 // (a state-bounded solve's resume workspace follows it: its duals stay in the lane launch's workspace)
 constexpr int kTailMaxSlots = 65536;
 constexpr size_t kTailBytes = 256 + static_cast<size_t>(kTailMaxSlots) * 24;
-size_t solver_workspace_bytes(const mmpc_model_info& mi, int nq, int64_t B) {
-    return (std::max(workspace_bytes(mi, nq, B), group_workspace_bytes(mi, B)) + 255) / 256 * 256;
-}
-
-int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
-                  int barrier_rule = MMPC_BARRIER_MONOTONE);
 
 // Iteration-tail hand-over of a lane-kernel solve: the lane kernel's wave runs until its slowest lane
 // converges (cfg#3: 1 % of the instances need a 5th iteration, and the waves holding them set the kernel time), so
@@ -953,30 +902,30 @@ struct TailPlan {
     int cap = 0, wave_max = 0, slots = 0, gpw = 1;
     size_t lds = 0, xb_ws_bytes = 0;
 };
-TailPlan tail_plan(const mmpc_handle* h, const SolveParams& p, bool bounded, int cu) {
+// mi: the model at the horizon of the launch; v: the lane launch's key; cu <= 0 (no device queried, or a solve that must
+// stay in the lane kernel: the diagnostic trace): no hand-over
+TailPlan tail_plan(const mmpc_handle* h, const mmpc_model_info& mi, int64_t B, const KernelVariant& v, int cu) {
     TailPlan t;
-    const mmpc_model_info mi = with_horizon(h->info, p.N);   // the horizon of the launch (a pinned solve's is shorter)
-    const bool xb = p.x_bounded != 0;
-    if (mi.is_linear || p.trace || cu <= 0) return t;
+    if (mi.is_linear || cu <= 0) return t;
     if (mi.num_x + mi.num_u >= kGroupLanes) return t;
     constexpr int kNoCap = 1 << 20;
     // bounded solves (state: interior point; control: projected SQP with its QP re-solves) hand over by the wave rule
     // alone: their counts spread (exo |u| <= 0.5: 4.3 mean, 12 max), and a cap either hands over too many or none
-    const bool spread = xb || bounded;
+    const bool spread = v.xb || v.ub;
+    const int max_iter = h->opts.max_iter;
     // opts.tail_* (ABI 6), the MMPC_TAIL_* environment overriding them (A/B and tests); -1: the default policy
     const int cap_o = h->tail_cap_env >= 0 ? h->tail_cap_env : h->opts.tail_cap;
     const int wave_o = h->tail_wave_env >= 0 ? h->tail_wave_env : h->opts.tail_wave_max;
     const int rounds_o = h->tail_rounds_env > 0 ? h->tail_rounds_env : h->opts.tail_rounds;
     const int cap = cap_o >= 0 ? cap_o : (spread ? kNoCap : 4);
-    if (cap <= 0 || (cap >= p.max_iter && !spread)) return t;
+    if (cap <= 0 || (cap >= max_iter && !spread)) return t;
     // wave rule threshold: 8 lanes (unbounded: only the thin tails of loose tolerances use it), 4 for bounded solves,
     // whose handed-over instances need several more iterations (exo at cfg#3 size, ms without / with 4: |qdot| <= 1.5
     // 65.3 / 60.5 (1 / 2 / 3 / 6 lanes: 62.2 / 61.0 / 61.0 / 67.6, profiles/r05/xbwave); |u| <= 0.5 36.9 / 30.1, |u| <= 2
     // 22.7 / 22.2 (8 lanes: 38.4 / 21.0; caps 4-8 beside it, profiles/r05/ubsweep))
     const int wave_max = wave_o >= 0 ? wave_o : (spread ? 4 : 8);
-    if (spread && cap >= p.max_iter && wave_max <= 0) return t;
-    const size_t inst = static_cast<size_t>(group_lds_doubles(mi.num_x, mi.num_u, h->nq, mi.num_shooting_nodes,
-                                                              bounded && !xb, false, xb)) * sizeof(double);
+    if (spread && cap >= max_iter && wave_max <= 0) return t;
+    const size_t inst = group_lds_instance_bytes(mi, h->nq, v);
     if (inst > 64 * 1024) return t;
     const int gpw = static_cast<int>(std::max<size_t>(1, std::min<size_t>(kGroupsPerWave, (64 * 1024) / inst)));
     const int per_cu = static_cast<int>(std::min<size_t>(4, (160 * 1024) / (gpw * inst)));
@@ -986,10 +935,8 @@ TailPlan tail_plan(const mmpc_handle* h, const SolveParams& p, bool bounded, int
     t.lds = gpw * inst;
     // up to four rounds of resume workgroups (slots nobody claimed exit at once, so spare slots cost nothing)
     const int rounds = rounds_o > 0 ? rounds_o : 4;
-    t.slots = static_cast<int>(std::min<int64_t>({p.B, kTailMaxSlots, (int64_t)rounds * per_cu * cu * gpw}));
-    if (xb)
-        t.xb_ws_bytes = static_cast<size_t>(group_ws_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, false, true)) *
-                        static_cast<size_t>(t.slots) * sizeof(double);
+    t.slots = static_cast<int>(std::min<int64_t>({B, kTailMaxSlots, (int64_t)rounds * per_cu * cu * gpw}));
+    if (v.xb) t.xb_ws_bytes = static_cast<size_t>(group_ws_doubles(mi, v)) * static_cast<size_t>(t.slots) * sizeof(double);
     return t;
 }
 // the device's compute units (the resume launch's slots scale with them), queried once per handle
@@ -1003,8 +950,47 @@ int query_cu_count(mmpc_handle* h) {
     return MMPC_OK;
 }
 
-// u_lb / u_ub rows of the *_bounds entry points: 0 = one shared [nu] row, >= nu = a row per instance.  Pure
-// arithmetic: every entry point checks it before its first device call.
+// The handle's workspace, byte offsets:
+//   [solver workspace | hand-over list | resume workspace]  (one launch, horizon N)  ...  | staging
+// The first three are what one launch at horizon N under the key v uses; `end` is what that launch needs allocated.
+// A pinned solve (mmpc_solve_batch_pinned) runs the solver at horizon N - m, where those regions end at an offset that
+// depends on m (the resume slots grow as the stage data shrink), so its staging area -- x0' [B][nx], u_prev' [B][nu],
+// traj' [B][N - m][nx], V' [B][NV(N - m)], sized for m = 1, the worst case -- lies after the largest end over every
+// horizon 1..N (reserved_layout, which alone fills the second row; what mmpc_reserve_workspace reserves is `total`).
+struct WorkspaceLayout {
+    TailPlan tail;
+    size_t solver = 0, tail_list = 0, resume = 0, end = 0;
+    size_t max_end = 0, staging = 0, total = 0;
+};
+WorkspaceLayout workspace_layout(const mmpc_handle* h, const mmpc_model_info& mi, int64_t B, const KernelVariant& v,
+                                 int cu) {
+    WorkspaceLayout L;
+    L.tail = tail_plan(h, mi, B, v, cu);
+    L.tail_list = L.solver + solver_workspace_bytes(mi, h->nq, B);
+    L.resume = L.tail_list + kTailBytes;
+    L.end = L.resume + L.tail.xb_ws_bytes;
+    return L;
+}
+// every horizon under the key with the largest end (state bounds: the only one with a resume workspace), reserved
+// whether or not the handle has state bounds or pins now: neither mmpc_set_state_bounds nor a pinned solve may make a
+// later solve grow the workspace (a hipFree / hipMalloc inside a stream-ordered solve, or under a captured hipGraph
+// that still points at the old buffer)
+WorkspaceLayout reserved_layout(const mmpc_handle* h, int64_t B, int cu) {
+    const mmpc_model_info& mi = h->info;
+    WorkspaceLayout L;   // ends as the handle's own horizon's
+    size_t max_end = 0;
+    for (int n = 1; n <= mi.num_shooting_nodes; ++n) {
+        L = workspace_layout(h, with_horizon(mi, n), B, kVariantXb, cu);
+        max_end = std::max(max_end, L.end);
+    }
+    L.max_end = max_end;
+    const size_t nx = mi.num_x, nu = mi.num_u, N1 = mi.num_shooting_nodes > 1 ? mi.num_shooting_nodes - 1 : 0;
+    L.staging = (L.max_end + 255) / 256 * 256;
+    L.total = L.staging + static_cast<size_t>(B) * (nx + nu + N1 * nx + nx * (N1 + 1) + nu * N1) * sizeof(double);
+    return L;
+}
+
+// u_lb / u_ub rows of the *_bounds entry points: 0 = one shared [nu] row, >= nu = a row per instance.
 int check_bounds_stride(const mmpc_model_info& mi, int64_t b_stride) {
     if (b_stride != 0 && b_stride < mi.num_u)
         return fail(MMPC_ERR_INVALID_ARG, "bounds_stride must be 0 (shared) or >= nu (" + std::to_string(mi.num_u) +
@@ -1013,8 +999,7 @@ int check_bounds_stride(const mmpc_model_info& mi, int64_t b_stride) {
         return fail(MMPC_ERR_UNSUPPORTED, "bounds_stride above 2^31 - 1 is not supported");
     return MMPC_OK;
 }
-
-// u_pin / n_pin of the *_pinned entry points.  Pure arithmetic, like check_bounds_stride: checked before any device call.
+// u_pin / n_pin of the *_pinned entry points
 int check_pins(const mmpc_model_info& mi, const double* u_pin, int32_t n_pin) {
     const int N = mi.num_shooting_nodes;
     if (n_pin < 0 || n_pin > N - 1)
@@ -1028,43 +1013,45 @@ int check_pins(const mmpc_model_info& mi, const double* u_pin, int32_t n_pin) {
     return MMPC_OK;
 }
 
-// Workspace of a handle with the pinned solves' staging area.  A pinned solve runs the solver at horizon N - m, whose
-// workspace, hand-over list and resume workspace end at an offset that depends on m (the resume slots grow as the
-// stage data shrink), so the staging area lies after the largest of them over every horizon 1..N:
-//   [solver workspace | hand-over list | resume workspace]  (what launch_kernel lays out, any horizon)  | staging
-// staging: x0' [B][nx], u_prev' [B][nu], traj' [B][N - m][nx], V' [B][NV(N - m)]; sized for m = 1, the worst case.
-size_t solve_workspace_bytes_max(const mmpc_handle* h, int64_t B, int cu) {
-    size_t mx = 0;
-    for (int n = 1; n <= h->info.num_shooting_nodes; ++n) {
-        SolveParams p{};
-        p.B = B;
-        p.N = n;
-        p.max_iter = h->opts.max_iter;
-        p.x_bounded = 1;
-        p.is_linear = h->info.is_linear;
-        mx = std::max(mx, solver_workspace_bytes(with_horizon(h->info, n), h->nq, B) + kTailBytes +
-                              tail_plan(h, p, false, cu).xb_ws_bytes);
-    }
-    return (mx + 255) / 256 * 256;
-}
-size_t pin_staging_bytes(const mmpc_model_info& mi, int64_t B) {
-    const size_t nx = mi.num_x, nu = mi.num_u, N1 = mi.num_shooting_nodes > 1 ? mi.num_shooting_nodes - 1 : 0;
-    return static_cast<size_t>(B) * (nx + nu + N1 * nx + nx * (N1 + 1) + nu * N1) * sizeof(double);
+// One solve as the C-ABI describes it, in the order of the entry points' parameters (device or host pointers, as the
+// entry point takes them).
+struct SolveArgs {
+    int64_t B = 0;
+    const double *x0 = nullptr, *u_prev = nullptr, *traj = nullptr, *weights = nullptr;
+    int64_t weights_stride = 0;
+    const double *u_lb = nullptr, *u_ub = nullptr;
+    int64_t bounds_stride = 0;
+    const double* u_pin = nullptr;
+    int32_t n_pin = 0;
+    double* V = nullptr;
+    int32_t *status = nullptr, *iters = nullptr;
+    double *kkt = nullptr, *u0_out = nullptr;
+    hipStream_t stream = nullptr;
+    double* trace = nullptr;
+};
+// The one check of a solve's arguments.  Pure arithmetic on the arguments and the model (info: null for a null handle):
+// every solve entry point calls it first, before any device call, copy or send, and returns at once when B == 0.
+int check_solve_args(const mmpc_model_info* info, const SolveArgs& a, const char* null_handle = "null handle") {
+    if (!info) return fail(MMPC_ERR_INVALID_ARG, null_handle);
+    if (int rc = check_pins(*info, a.u_pin, a.n_pin)) return rc;
+    if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(*info, a.bounds_stride)) return rc;
+    if (a.B == 0) return MMPC_OK;
+    if (!a.x0 || !a.u_prev || !a.traj || !a.weights || !a.V) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
+    // rows of weights_stride are read (and, by the host and RCCL entries, copied and sent) for every instance
+    if (a.weights_stride != 0 && a.weights_stride < info->num_x + 2 * info->num_u)
+        return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
+    if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
+    return MMPC_OK;
 }
 
-int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
-                 const double* weights, int64_t w_stride, const double* u_lb, const double* u_ub, double* V,
-                 int32_t* status, int32_t* iters, double* kkt, hipStream_t stream, double* trace = nullptr,
-                 double* u0_out = nullptr, int64_t b_stride = 0, const double* u_pin = nullptr, int n_pin = 0) {
+int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, int barrier_rule, hipStream_t stream);
+
+// a solve whose arguments check_solve_args has passed, B > 0, device pointers, on the current device
+int launch_solve(mmpc_handle* h, const SolveArgs& a) {
     const mmpc_model_info& mi = h->info;
-    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
-    const int nw = mi.num_x + 2 * mi.num_u;
-    if (w_stride != 0 && w_stride < nw) return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
-    if (int rc = check_bounds_stride(mi, b_stride)) return rc;
-    if (B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
-    SolveParams p;
+    const int64_t B = a.B;
+    SolveParams p{};
     p.B = B;
     p.N = mi.num_shooting_nodes;
     p.max_iter = h->opts.max_iter;
@@ -1072,35 +1059,25 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     p.tol_grad = h->opts.tol_grad;
     p.tol_defect = h->opts.tol_defect;
     p.is_linear = mi.is_linear;
-    p.x0 = x0;
-    p.u_prev = u_prev;
-    p.traj = traj;
-    p.weights = weights;
-    p.w_stride = w_stride;
-    p.u_lb = u_lb;
-    p.u_ub = u_ub;
-    p.b_stride = static_cast<int32_t>(b_stride);
-    p.V = V;
-    p.status = status;
-    p.iters = iters;
-    p.kkt = kkt;
-    p.trace = trace;
-    p.u0_out = u0_out;
+    p.x0 = a.x0;
+    p.u_prev = a.u_prev;
+    p.traj = a.traj;
+    p.weights = a.weights;
+    p.w_stride = a.weights_stride;
+    // any bound pointer selects a bounded kernel (launch_kernel); host entry points pass NULL for bounds that are all
+    // infinite
+    p.u_lb = a.u_lb;
+    p.u_ub = a.u_ub;
+    p.b_stride = static_cast<int32_t>(a.bounds_stride);
+    p.V = a.V;
+    p.status = a.status;
+    p.iters = a.iters;
+    p.kkt = a.kkt;
+    p.trace = a.trace;
+    p.u0_out = a.u0_out;
     p.init_hold = h->opts.init_states == MMPC_INIT_HOLD_X0;
     p.init_zero = h->opts.init_states == MMPC_INIT_ZERO;
-    p.tail_cap = 0;
-    p.tail_wave_max = 0;
-    p.tail_slots = 0;
-    p.tail_count = p.tail_idx = p.tail_it = nullptr;
-    p.tail_mu = p.tail_mub = nullptr;
-    p.tail_lws = nullptr;
-    p.no_release = 0;
-    p.tail_lws_block = 0;
-    p.tail_lws_ss = p.tail_lws_zl = 0;
     p.gpw = kGroupsPerWave;
-    // any bound pointer selects the kernels' BOUNDED variant (projected GN-SQP, sqp_wave.h); host entry
-    // points pass NULL for bounds that are all infinite
-    const bool bounded = u_lb || u_ub;
     int barrier_rule;
     {  // state bounds: the interior-point variant (sqp_wave.h "state bounds"), by value in the launch arguments
         std::lock_guard<std::mutex> lk(h->xb_mu);
@@ -1112,17 +1089,16 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
         }
     }
     const int solver = resolve_kkt_solver(h, B);   // for the handle's own N, pinned or not
-    if (n_pin == 0) return launch_kernel(h, solver, p, bounded, stream, barrier_rule);
+    if (a.n_pin == 0) return launch_kernel(h, solver, p, barrier_rule, a.stream);
     // committed controls: prologue (rollout of the pins, gather of the tail problem), the solve of the staged
     // horizon-(N - m) problem, epilogue (its solution back into V, u0_out = the first pin)
-    if (int rc = check_pins(mi, u_pin, n_pin)) return rc;
     if (int rc = query_cu_count(h)) return rc;
-    const int m = n_pin, N = mi.num_shooting_nodes, Np = N - m, nx = mi.num_x, nu = mi.num_u;
-    const size_t base = solve_workspace_bytes_max(h, B, h->cu_count);
+    const int m = a.n_pin, N = mi.num_shooting_nodes, Np = N - m, nx = mi.num_x, nu = mi.num_u;
+    const WorkspaceLayout L = reserved_layout(h, B, h->cu_count);
     double* ws = nullptr;
-    if (int rc = ensure_workspace_bytes(h, base + pin_staging_bytes(mi, B), &ws)) return rc;
+    if (int rc = ensure_workspace_bytes(h, L.total, &ws)) return rc;
     const int64_t nvs = static_cast<int64_t>(nx) * (Np + 1) + static_cast<int64_t>(nu) * Np;
-    double* const x0s = ws + base / sizeof(double);
+    double* const x0s = ws + L.staging / sizeof(double);
     double* const ups = x0s + B * nx;
     double* const trajs = ups + B * nu;
     double* const Vs = trajs + B * Np * nx;
@@ -1130,12 +1106,12 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     if (std::max(n_gather, n_scatter) > 0x7fffffffLL * 256) return fail(MMPC_ERR_INVALID_ARG, "B*N too large");
     int rc = with_model(mi.model_id, [&](auto* mp) {
         using M = std::remove_pointer_t<decltype(mp)>;
-        pin_rollout_kernel<M><<<grid1d(B, 256), 256, 0, stream>>>(B, N, m, mi.step_size, x0, u_pin, V, x0s, ups);
+        pin_rollout_kernel<M><<<grid1d(B, 256), 256, 0, a.stream>>>(B, N, m, mi.step_size, a.x0, a.u_pin, a.V, x0s, ups);
         return static_cast<int>(MMPC_OK);
     });
     if (rc) return rc;
-    pin_gather_kernel<<<grid1d(n_gather, 256), 256, 0, stream>>>(B, N, m, nx, nu, traj, V, trajs,
-                                                                  p.init_zero ? nullptr : Vs);
+    pin_gather_kernel<<<grid1d(n_gather, 256), 256, 0, a.stream>>>(B, N, m, nx, nu, a.traj, a.V, trajs,
+                                                                    p.init_zero ? nullptr : Vs);
     MMPC_HIP(hipGetLastError());
     p.N = Np;
     p.x0 = x0s;
@@ -1143,136 +1119,144 @@ int launch_solve(mmpc_handle* h, int64_t B, const double* x0, const double* u_pr
     p.traj = trajs;
     p.V = Vs;
     p.u0_out = nullptr;
-    if ((rc = launch_kernel(h, solver, p, bounded, stream, barrier_rule))) return rc;
-    pin_scatter_kernel<<<grid1d(n_scatter, 256), 256, 0, stream>>>(B, N, m, nx, nu, Vs, u_pin, V, u0_out);
+    if ((rc = launch_kernel(h, solver, p, barrier_rule, a.stream))) return rc;
+    pin_scatter_kernel<<<grid1d(n_scatter, 256), 256, 0, a.stream>>>(B, N, m, nx, nu, Vs, a.u_pin, a.V, a.u0_out);
     MMPC_HIP(hipGetLastError());
     return MMPC_OK;
 }
 
-// one kernel launch for solver (not AUTO) on p.B instances
-int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, bool bounded, hipStream_t stream,
-                  int barrier_rule) {
-    // every size below follows the horizon of the launch, p.N: the handle's, or N - n_pin of a pinned solve (the
-    // kernels lay their LDS and workspace out from p.N, and host and kernel must agree on one horizon)
-    const mmpc_model_info mi = with_horizon(h->info, p.N);
-    const int64_t B = p.B;
+// The three launches of launch_kernel.  Every size follows the horizon of the launch, p.N: the handle's, or N - n_pin of a
+// pinned solve (the kernels lay their LDS and workspace out from p.N, and host and kernel must agree on one horizon).
+int launch_condensed(mmpc_handle* h, const SolveParams& p, const KernelVariant& v, hipStream_t stream) {
+    if (v.xb) return fail(MMPC_ERR_UNSUPPORTED, "state bounds need a Riccati solver (MMPC_KKT_RICCATI[_GROUP])");
+    if (v.fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 is a Riccati-solver option");
+#if MMPC_BUILTIN_MODELS
+    // host-side shape checks: the kernel holds one condensed-Hessian row per lane
+    // (supported or not by the handle's own N: a pinned solve runs the size class of its shorter horizon)
+    if (h->info.model_id != MMPC_MODEL_TWO_LINK_ARM || h->info.num_shooting_nodes * TwoLinkArm::NU > 64)
+        return fail(MMPC_ERR_UNSUPPORTED, "condensed solver needs the 2-link arm and N*nu <= 64");
     const int N = p.N;
+    dim3 grid(static_cast<unsigned>(p.B)), block(64);
+    if (v.ub) {
+        if (N <= 16) sqp_wave_kernel<TwoLinkArm, 16, true><<<grid, block, 0, stream>>>(p);
+        else if (N <= 30) sqp_wave_kernel<TwoLinkArm, 30, true><<<grid, block, 0, stream>>>(p);
+        else sqp_wave_kernel<TwoLinkArm, 32, true><<<grid, block, 0, stream>>>(p);
+    } else {
+        if (N <= 16) sqp_wave_kernel<TwoLinkArm, 16><<<grid, block, 0, stream>>>(p);
+        else if (N <= 30) sqp_wave_kernel<TwoLinkArm, 30><<<grid, block, 0, stream>>>(p);
+        else sqp_wave_kernel<TwoLinkArm, 32><<<grid, block, 0, stream>>>(p);
+    }
+    MMPC_HIP(hipGetLastError());
+    return MMPC_OK;
+#else
+    return fail(MMPC_ERR_UNSUPPORTED, "condensed solver needs the built-in 2-link arm");
+#endif
+}
+
+int launch_group(mmpc_handle* h, const SolveParams& p, const KernelVariant& v, hipStream_t stream) {
+    const mmpc_model_info mi = with_horizon(h->info, p.N);
+    if (v.fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 needs the lane Riccati solver");
+    const size_t lds = group_lds_bytes(mi, h->nq, v);
+    if (lds > kMaxGroupLds) return fail(MMPC_ERR_UNSUPPORTED, "group Riccati solver: stage data exceeds 160 KB LDS");
+    const WorkspaceLayout L = workspace_layout(h, mi, p.B, v, 0);   // cu = 0: nothing is handed over
+    double* ws = nullptr;
+    if (int rc = ensure_workspace_bytes(h, L.end, &ws)) return rc;
+    const GroupWork gwk{ws + L.solver / sizeof(double)};
+    const dim3 grid(grid1d(p.B, kGroupsPerWave)), block(64);
+    return with_model(mi.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        return launch_group_of<M>(v, grid, block, lds, stream, p, gwk, "group kernel launch");
+    });
+}
+
+// the lane launch, then (TailPlan) the 16-lane resume launch over the instances it handed over
+int launch_lane(mmpc_handle* h, const SolveParams& p, const KernelVariant& v, hipStream_t stream) {
+    const mmpc_model_info mi = with_horizon(h->info, p.N);
+    if (int rc = query_cu_count(h)) return rc;
+    // the diagnostic trace keeps every instance in the lane kernel
+    const WorkspaceLayout L = workspace_layout(h, mi, p.B, v, p.trace ? 0 : h->cu_count);
+    const TailPlan& tp = L.tail;
+    double* ws = nullptr;
+    if (int rc = ensure_workspace_bytes(h, L.end, &ws)) return rc;
+    char* const base = reinterpret_cast<char*>(ws);
+    const LaneWork lw{reinterpret_cast<double*>(base + L.solver)};
+    SolveParams pl = p;
+    if (tp.cap > 0) {   // the lane kernel hands instances still unconverged at iteration cap to a 16-lane launch
+        pl.tail_cap = tp.cap;
+        pl.tail_wave_max = tp.wave_max;
+        pl.tail_slots = tp.slots;
+        pl.tail_count = reinterpret_cast<int32_t*>(base + L.tail_list);
+        pl.tail_idx = reinterpret_cast<int32_t*>(base + L.tail_list + 256);
+        pl.tail_it = pl.tail_idx + kTailMaxSlots;
+        pl.tail_mu = reinterpret_cast<double*>(pl.tail_it + kTailMaxSlots);
+        pl.tail_mub = pl.tail_mu + kTailMaxSlots;
+        MMPC_HIP(hipMemsetAsync(pl.tail_count, 0, sizeof(int32_t), stream));
+    }
+    // lane kernels: their own translation unit (lane_kernels.hip, lane_launch.h)
+    const int lrc = launch_lane_kernels(mi.model_id, v, dim3(grid1d(p.B, 64)), dim3(64), stream, pl, lw);
+    if (lrc == -1) return fail(MMPC_ERR_UNSUPPORTED, "model not compiled into this library");
+    if (lrc != 0) return fail(MMPC_ERR_UNSUPPORTED, "lane Riccati solver: no kernel of this model for the solve's variant");
+    MMPC_HIP(hipGetLastError());
+    if (tp.cap <= 0) return MMPC_OK;
+    // resume launch over the hand-over list (slots the lane kernel did not claim exit at once), with the fp64 factor
+    SolveParams pr = pl;
+    pr.tail_cap = 0;
+    pr.gpw = tp.gpw;
+    pr.init_hold = pr.init_zero = 0;   // the handed-over iterate is in V
+    pr.no_release = 1;                 // control bounds: the lane kernel's active-set rule
+    KernelVariant rv = v;
+    rv.fp32 = false;
+    GroupWork gwk{lw.ws};
+    if (v.xb) {   // duals from the lane workspace; the resume workspace after the hand-over list
+        pr.tail_lws = lw.ws;
+        pr.tail_lws_block = static_cast<int64_t>(lane_ws_doubles(mi, h->nq, v)) * 64;
+        pr.tail_lws_ss = lane_stage_stride(mi.num_x, mi.num_u, v.xb);
+        pr.tail_lws_zl = lane_zl_offset(mi.num_x, mi.num_u);
+        gwk.ws = reinterpret_cast<double*>(base + L.resume);
+    }
+    const dim3 rgrid(static_cast<unsigned>((tp.slots + tp.gpw - 1) / tp.gpw)), rblock(64);
+    return with_model(mi.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        return launch_group_of<M>(rv, rgrid, rblock, tp.lds, stream, pr, gwk, "resume launch");
+    });
+}
+
+// The key of a solve (kernel_variant.h), built here and nowhere else, in canonical form: the interior point takes the
+// control bounds of a state-bounded solve, per-instance rows matter to bounded kernels only, the barrier rule to the
+// interior point only, and the fp32 factor runs Gauss-Newton.  <0: resolve_hessian's error.
+int kernel_variant(const mmpc_handle* h, int solver, const SolveParams& p, int barrier_rule, KernelVariant* v) {
+    const bool u_bounded = p.u_lb || p.u_ub;
+    const int hess = resolve_hessian(h, solver, u_bounded);   // EXACT requested on an unsupported solver: error
+    if (hess < 0) return hess;
+    v->xb = p.x_bounded != 0;
+    v->ub = u_bounded && !v->xb;
+    v->fp32 = h->opts.factor_fp32 != 0;
+    v->exact = hess == MMPC_HESSIAN_EXACT && !v->fp32;
+    v->instb = p.b_stride != 0 && (v->ub || v->xb);
+    v->mehr = v->xb && barrier_rule == MMPC_BARRIER_MEHROTRA;
+    return MMPC_OK;
+}
+
+// one solve of p.B instances with solver (not AUTO): the condensed launch, the 16-lane launch, or the lane launch with
+// its resume launch
+int launch_kernel(mmpc_handle* h, int solver, const SolveParams& p, int barrier_rule, hipStream_t stream) {
+    KernelVariant v;
+    if (int rc = kernel_variant(h, solver, p, barrier_rule, &v)) return rc;
     // the barrier rule matters to the interior point alone (finite state bounds); Mehrotra's rule is built into the
     // 16-lane kernel for nonlinear solves -- anything else is refused, never run under the other rule
-    const bool mehr = p.x_bounded != 0 && barrier_rule == MMPC_BARRIER_MEHROTRA;
-    if (mehr && mi.is_linear)
+    if (v.mehr && h->info.is_linear)
         return fail(MMPC_ERR_UNSUPPORTED, "barrier rule MEHROTRA: not available in linear mode "
                                           "(use MMPC_BARRIER_MONOTONE)");
-    if (mehr && solver != MMPC_KKT_RICCATI_GROUP)
+    if (v.mehr && solver != MMPC_KKT_RICCATI_GROUP)
         return fail(MMPC_ERR_UNSUPPORTED,
                     std::string("barrier rule MEHROTRA: needs the 16-lane solver (MMPC_KKT_RICCATI_GROUP), this solve ") +
                         (h->opts.kkt_solver == MMPC_KKT_AUTO ? "resolves to" : "asks for") +
                         (solver == MMPC_KKT_RICCATI ? " the lane solver (MMPC_KKT_RICCATI)" : " the condensed solver"));
-    if (solver == MMPC_KKT_RICCATI_GROUP) {
-        if (h->opts.factor_fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 needs the lane Riccati solver");
-        const bool xb = p.x_bounded != 0;
-        const size_t lds = group_lds_bytes(mi, h->nq, bounded, xb);
-        if (lds > kMaxGroupLds) return fail(MMPC_ERR_UNSUPPORTED, "group Riccati solver: stage data exceeds 160 KB LDS");
-        LaneWork lw;
-        int rc = ensure_workspace_bytes(h, solver_workspace_bytes(mi, h->nq, B) + kTailBytes, &lw.ws);
-        if (rc) return rc;
-        GroupWork gwk{lw.ws};
-        dim3 grid(grid1d(B, kGroupsPerWave)), block(64);
-        const int hess = resolve_hessian(h, solver, bounded);
-        if (hess < 0) return hess;
-        rc = with_model(mi.model_id, [&](auto* m) {
-            using M = std::remove_pointer_t<decltype(m)>;
-            if (mehr)
-                return dispatch_group_mehrotra<M>(hess == MMPC_HESSIAN_EXACT, grid, block, lds, stream, p, gwk);
-            return dispatch_group<M>(bounded && !xb, xb, hess == MMPC_HESSIAN_EXACT, grid, block, lds, stream, p, gwk,
-                                     "group kernel launch");
-        });
-        if (rc) return rc;
-        MMPC_HIP(hipGetLastError());
-        return MMPC_OK;
+    switch (solver) {
+        case MMPC_KKT_RICCATI_GROUP: return launch_group(h, p, v, stream);
+        case MMPC_KKT_CONDENSED: return launch_condensed(h, p, v, stream);
+        default: return launch_lane(h, p, v, stream);
     }
-    if (p.x_bounded && solver == MMPC_KKT_CONDENSED)
-        return fail(MMPC_ERR_UNSUPPORTED, "state bounds need a Riccati solver (MMPC_KKT_RICCATI[_GROUP])");
-    const int hess = resolve_hessian(h, solver, bounded);   // EXACT requested on an unsupported solver: error
-    if (hess < 0) return hess;
-    if (solver == MMPC_KKT_CONDENSED) {
-        if (h->opts.factor_fp32) return fail(MMPC_ERR_UNSUPPORTED, "factor_fp32 is a Riccati-solver option");
-#if MMPC_BUILTIN_MODELS
-        // host-side shape checks: the kernel holds one condensed-Hessian row per lane
-        // (supported or not by the handle's own N: a pinned solve runs the size class of its shorter horizon)
-        if (mi.model_id != MMPC_MODEL_TWO_LINK_ARM || h->info.num_shooting_nodes * TwoLinkArm::NU > 64)
-            return fail(MMPC_ERR_UNSUPPORTED, "condensed solver needs the 2-link arm and N*nu <= 64");
-        dim3 grid(static_cast<unsigned>(B)), block(64);
-        if (bounded) {
-            if (N <= 16) sqp_wave_kernel<TwoLinkArm, 16, true><<<grid, block, 0, stream>>>(p);
-            else if (N <= 30) sqp_wave_kernel<TwoLinkArm, 30, true><<<grid, block, 0, stream>>>(p);
-            else sqp_wave_kernel<TwoLinkArm, 32, true><<<grid, block, 0, stream>>>(p);
-        } else {
-            if (N <= 16) sqp_wave_kernel<TwoLinkArm, 16><<<grid, block, 0, stream>>>(p);
-            else if (N <= 30) sqp_wave_kernel<TwoLinkArm, 30><<<grid, block, 0, stream>>>(p);
-            else sqp_wave_kernel<TwoLinkArm, 32><<<grid, block, 0, stream>>>(p);
-        }
-#else
-        return fail(MMPC_ERR_UNSUPPORTED, "condensed solver needs the built-in 2-link arm");
-#endif
-    } else {
-        int rc = query_cu_count(h);
-        if (rc) return rc;
-        const TailPlan tp = tail_plan(h, p, bounded, h->cu_count);
-        LaneWork lw;
-        rc = ensure_workspace_bytes(h, solver_workspace_bytes(mi, h->nq, B) + kTailBytes + tp.xb_ws_bytes, &lw.ws);
-        if (rc) return rc;
-        dim3 grid(grid1d(B, 64)), block(64);
-        SolveParams pl = p;
-        if (tp.cap > 0) {   // the lane kernel hands instances still unconverged at iteration cap to a 16-lane launch
-            char* const tb = reinterpret_cast<char*>(lw.ws) + solver_workspace_bytes(mi, h->nq, B);
-            pl.tail_cap = tp.cap;
-            pl.tail_wave_max = tp.wave_max;
-            pl.tail_slots = tp.slots;
-            pl.tail_count = reinterpret_cast<int32_t*>(tb);
-            pl.tail_idx = reinterpret_cast<int32_t*>(tb + 256);
-            pl.tail_it = pl.tail_idx + kTailMaxSlots;
-            pl.tail_mu = reinterpret_cast<double*>(pl.tail_it + kTailMaxSlots);
-            pl.tail_mub = pl.tail_mu + kTailMaxSlots;
-            MMPC_HIP(hipMemsetAsync(pl.tail_count, 0, sizeof(int32_t), stream));
-        }
-        // lane kernels: their own translation unit (lane_kernels.hip, lane_launch.h)
-        if (launch_lane_kernels(mi.model_id, h->opts.factor_fp32 != 0, bounded, p.x_bounded != 0,
-                                hess == MMPC_HESSIAN_EXACT, grid, block, stream, pl, lw) != 0)
-            return fail(MMPC_ERR_UNSUPPORTED, "model not compiled into this library");
-        if (tp.cap > 0) {   // resume launch over the hand-over list (slots the lane kernel did not claim exit at once)
-            MMPC_HIP(hipGetLastError());
-            SolveParams pr = pl;
-            pr.tail_cap = 0;
-            pr.gpw = tp.gpw;
-            pr.init_hold = pr.init_zero = 0;   // the handed-over iterate is in V
-            pr.no_release = 1;                 // control bounds: the lane kernel's active-set rule
-            const bool xb = p.x_bounded != 0;
-            const bool ub = bounded && !xb;
-            GroupWork gwk{lw.ws};
-            if (xb) {   // duals from the lane workspace; the resume workspace after the hand-over list
-                const int nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes;
-                pr.tail_lws = lw.ws;
-                pr.tail_lws_block = static_cast<int64_t>(lane_ws_doubles(nx, nu, h->nq, N, true)) * 64;
-                pr.tail_lws_ss = lane_stage_stride(nx, nu, true);
-                pr.tail_lws_zl = lane_zl_offset(nx, nu);
-                gwk.ws = lw.ws + (solver_workspace_bytes(mi, h->nq, B) + kTailBytes) / sizeof(double);
-            }
-            dim3 rgrid(static_cast<unsigned>((tp.slots + tp.gpw - 1) / tp.gpw)), rblock(64);
-            rc = with_model(mi.model_id, [&](auto* m) {
-                using M = std::remove_pointer_t<decltype(m)>;
-                if constexpr (M::NX + M::NU < kGroupLanes) {
-                    return dispatch_group<M>(ub, xb, hess == MMPC_HESSIAN_EXACT, rgrid, rblock, tp.lds, stream, pr, gwk,
-                                             "resume launch");
-                } else {
-                    return fail(MMPC_ERR_UNSUPPORTED, "tail hand-over: nx + nu >= 16");   // tail_plan excludes it
-                }
-            });
-            if (rc) return rc;
-        }
-    }
-    MMPC_HIP(hipGetLastError());
-    return MMPC_OK;
 }
 
 int ensure_host_ctx(mmpc_handle* h, size_t bytes) {
@@ -1442,16 +1426,9 @@ int mmpc_get_barrier_rule(const mmpc_handle* h, int32_t* rule) {
 int mmpc_reserve_workspace(mmpc_handle* h, int64_t B, uint64_t* bytes) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    // + the tail hand-over list + a state-bounded solve's resume workspace (sized by the device's CUs: 256 until a
-    // device was queried), reserved whether or not the handle has state bounds now: a later mmpc_set_state_bounds must
-    // not make a solve grow the workspace (a hipFree / hipMalloc inside a stream-ordered solve, or under a captured
-    // hipGraph that still points at the old buffer)
-    auto total = [&]() {
-        const int cu = h->cu_count > 0 ? h->cu_count : 256;
-        // every horizon 1..N a pinned solve may run, then the pinned solves' staging area (reserved whether or not
-        // pins are ever used, as the Mehrotra record is)
-        return solve_workspace_bytes_max(h, B, cu) + pin_staging_bytes(h->info, B);
-    };
+    // reserved_layout: every horizon's solver workspace, hand-over list and resume workspace (sized by the device's CUs:
+    // 256 until a device was queried), then the pinned solves' staging area
+    auto total = [&]() { return reserved_layout(h, B, h->cu_count > 0 ? h->cu_count : 256).total; };
     if (bytes) *bytes = B == 0 ? 0 : total();
     if (B == 0) return MMPC_OK;
     int dev;
@@ -1484,40 +1461,25 @@ int mmpc_solve_batch_bounds(mmpc_handle* h, int64_t B, const double* x0, const d
                             const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                             int64_t bounds_stride, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res,
                             double* u0_out, void* stream) {
-    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
-    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;   // before any device call
-    if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
-    int dev;
-    int rc = resolve_device(h, &dev);
-    if (rc) return rc;
-    DeviceGuard g(dev);
-    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_solve(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, V_inout, status, iters,
-                        kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out, bounds_stride);
+    return mmpc_solve_batch_pinned(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, nullptr,
+                                   0, V_inout, status, iters, kkt_res, u0_out, stream);
 }
 
+// the device-pointer entry of every solve
 int mmpc_solve_batch_pinned(mmpc_handle* h, int64_t B, const double* x0, const double* u_prev, const double* traj,
                             const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                             int64_t bounds_stride, const double* u_pin, int32_t n_pin, double* V_inout,
                             int32_t* status, int32_t* iters, double* kkt_res, double* u0_out, void* stream) {
-    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
-    if (int rc = check_pins(h->info, u_pin, n_pin)) return rc;   // from the arguments alone, before any device call
-    if (n_pin == 0)
-        return mmpc_solve_batch_bounds(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride,
-                                       V_inout, status, iters, kkt_res, u0_out, stream);
-    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;
+    const SolveArgs a{B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, u_pin, n_pin, V_inout,
+                      status, iters, kkt_res, u0_out, reinterpret_cast<hipStream_t>(stream)};
+    if (int rc = check_solve_args(h ? &h->info : nullptr, a)) return rc;
     if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     int dev;
     int rc = resolve_device(h, &dev);
     if (rc) return rc;
     DeviceGuard g(dev);
     if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_solve(h, B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, V_inout, status, iters,
-                        kkt_res, reinterpret_cast<hipStream_t>(stream), nullptr, u0_out, bounds_stride, u_pin, n_pin);
+    return launch_solve(h, a);
 }
 
 int mmpc_host_alloc(uint64_t bytes, void** out) {
@@ -1558,12 +1520,11 @@ int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, co
                                  const double* traj, const double* weights, int64_t weights_stride,
                                  const double* u_lb, const double* u_ub, int64_t bounds_stride, const double* u_pin,
                                  int32_t n_pin, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res) {
-    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
-    if (int rc = check_pins(h->info, u_pin, n_pin)) return rc;   // from the arguments alone
-    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (int rc = check_bounds_stride(h->info, bounds_stride)) return rc;   // before the rows are scanned
+    SolveArgs a{B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, u_pin, n_pin, V_inout,
+                status, iters, kkt_res};
+    // before the bound rows are scanned and weights_stride sizes a copy
+    if (int rc = check_solve_args(h ? &h->info : nullptr, a)) return rc;
     if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     std::lock_guard<std::mutex> lk(h->host_mu);
     const mmpc_model_info& mi = h->info;
     const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
@@ -1605,10 +1566,10 @@ int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, co
     if (n_pin > 0) MMPC_HIP(hipMemcpyAsync(d + off_pin, u_pin, nP * sizeof(double), hipMemcpyHostToDevice, s));
     int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
     int32_t* dit = reinterpret_cast<int32_t*>(d + off_it);
-    rc = launch_solve(h, B, d + off_x0, d + off_up, d + off_tr, d + off_w, weights_stride, u_lb ? d + off_lb : nullptr,
-                      u_ub ? d + off_ub : nullptr, d + off_V, dst, dit, d + off_kkt, s, nullptr, nullptr,
-                      bounds_stride, n_pin > 0 ? d + off_pin : nullptr, n_pin);
-    if (rc) return rc;
+    a = SolveArgs{B, d + off_x0, d + off_up, d + off_tr, d + off_w, weights_stride, u_lb ? d + off_lb : nullptr,
+                  u_ub ? d + off_ub : nullptr, bounds_stride, n_pin > 0 ? d + off_pin : nullptr, n_pin, d + off_V, dst,
+                  dit, d + off_kkt, nullptr, s};   // the staged copies
+    if ((rc = launch_solve(h, a))) return rc;
     MMPC_HIP(hipMemcpyAsync(V_inout, d + off_V, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
     if (status) MMPC_HIP(hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (iters) MMPC_HIP(hipMemcpyAsync(iters, dit, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1930,12 +1891,11 @@ int mmpc_multi_solve_batch_host_pinned(mmpc_multi* m, int64_t B, const double* x
                                        const double* u_lb, const double* u_ub, int64_t bounds_stride,
                                        const double* u_pin, int32_t n_pin, double* V_inout, int32_t* status,
                                        int32_t* iters, double* kkt_res) {
-    if (!m) return fail(MMPC_ERR_INVALID_ARG, "null multi-device handle");
-    if (int rc = check_pins(m->h[0]->info, u_pin, n_pin)) return rc;   // before any shard starts
-    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (int rc = check_bounds_stride(m->h[0]->info, bounds_stride)) return rc;   // before any shard starts
+    const SolveArgs a{B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, u_pin, n_pin, V_inout,
+                      status, iters, kkt_res};
+    // before any shard starts
+    if (int rc = check_solve_args(m ? &m->h[0]->info : nullptr, a, "null multi-device handle")) return rc;
     if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     std::lock_guard<std::mutex> lk(m->mu);
     const mmpc_model_info& mi = m->h[0]->info;
     const int64_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
@@ -1997,20 +1957,15 @@ int mmpc_multi_solve_batch_rccl_bounds(mmpc_multi* m, int64_t B, const double* x
                                        const double* traj, const double* weights, int64_t weights_stride,
                                        const double* u_lb, const double* u_ub, int64_t bounds_stride, double* V_inout,
                                        int32_t* status, int32_t* iters, double* kkt_res, void* stream) {
-    if (!m) return fail(MMPC_ERR_INVALID_ARG, "null multi-device handle");
-    if (B < 0 || weights_stride < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0 or weights_stride < 0");
-    // checked before anything is sent: the scatter reads rows of bounds_stride
-    if (int rc = check_bounds_stride(m->h[0]->info, bounds_stride)) return rc;
+    const SolveArgs a{B, x0, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, nullptr, 0, V_inout,
+                      status, iters, kkt_res, nullptr, reinterpret_cast<hipStream_t>(stream)};
+    // checked before anything is sent: the scatter reads rows of bounds_stride and of weights_stride
+    if (int rc = check_solve_args(m ? &m->h[0]->info : nullptr, a, "null multi-device handle")) return rc;
     if (B == 0) return MMPC_OK;
-    if (!x0 || !u_prev || !traj || !weights || !V_inout) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
     if ((u_lb == nullptr) != (u_ub == nullptr)) return fail(MMPC_ERR_INVALID_ARG, "u_lb and u_ub go together");
     std::lock_guard<std::mutex> lk(m->mu);
     const mmpc_model_info& mi = m->h[0]->info;
     const int64_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v, nw = nx + 2 * nu;
-    // checked before anything is sent: the scatter reads rows of weights_stride (mmpc_solve_batch checks it too, but
-    // only after the shards have been sent)
-    if (weights_stride != 0 && weights_stride < nw)
-        return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 (shared) or >= nx + 2 nu");
     const int32_t G = static_cast<int32_t>(m->h.size());
     for (int32_t a = 0; a < G; ++a)
         for (int32_t b = 0; b < a; ++b)
@@ -2256,12 +2211,15 @@ int mmpc_debug_solve_trace(mmpc_handle* h, int64_t B, const double* x0, const do
                            const double* weights, int64_t weights_stride, double* V_inout, int32_t* status,
                            int32_t* iters, double* kkt_res, double* trace, void* stream) {
     if (!h || B < 0 || !trace) return fail(MMPC_ERR_INVALID_ARG, "bad argument");
+    const SolveArgs a{B, x0, u_prev, traj, weights, weights_stride, nullptr, nullptr, 0, nullptr, 0, V_inout, status,
+                      iters, kkt_res, nullptr, reinterpret_cast<hipStream_t>(stream), trace};
+    if (int rc = check_solve_args(&h->info, a)) return rc;
+    if (B == 0) return MMPC_OK;
     int dev;
     int rc = resolve_device(h, &dev);
     if (rc) return rc;
     DeviceGuard g(dev);
-    return launch_solve(h, B, x0, u_prev, traj, weights, weights_stride, nullptr, nullptr, V_inout, status, iters,
-                        kkt_res, reinterpret_cast<hipStream_t>(stream), trace);
+    return launch_solve(h, a);
 }
 
 }  // extern "C"

@@ -5,6 +5,9 @@
 * n_pin in {-1, N, N + 3}, and n_pin = 1 with a NULL u_pin, are MMPC_ERR_INVALID_ARG with the argument's name in
   mmpc_last_error on handles created without a device, on the device-pointer, the host and the multi-device entry:
   the pins are validated from the arguments alone, before any device call;
+* weights_stride < 0 or in 1 .. nx + 2 nu - 1 is MMPC_ERR_INVALID_ARG with `weights_stride` in mmpc_last_error on the
+  five solve entry points (the one check of a solve's arguments, check_solve_args in mmpc.hip), likewise before any
+  device call;
 * a linear-mode model with n_pin = 1 is MMPC_ERR_UNSUPPORTED;
 * the Python wrappers refuse a wrongly shaped u_pin with ValueError before the library is called."""
 import ctypes as C
@@ -74,6 +77,36 @@ def test_bad_pins_are_refused_by_the_multi_device_entry(mmpc_mod, tmp_path):
         rc = L.mmpc_multi_solve_batch_host_pinned(m._m, B, a(x0), a(up), a(tr), a(w), 0, None, None, 0, u_pin, n_pin,
                                                   a(V), None, None, None)
         assert rc == -1 and name in L.mmpc_last_error().decode(), (n_pin, rc, L.mmpc_last_error())
+    m.close()
+
+
+@pytest.mark.parametrize("model,nx,nu", MODELS)
+def test_bad_weights_stride_is_refused_by_every_solve_entry(model, nx, nu, mmpc_mod, tmp_path):
+    """weights_stride < 0 or in 1 .. nx + 2 nu - 1 is MMPC_ERR_INVALID_ARG naming the argument, from the arguments
+    alone (handles created without a device), on the five solve entry points: no entry sizes a copy or a send by it, or
+    goes to a device, before it is checked"""
+    N, B = 3, 5
+    p = mmpc_mod.write_model_json(str(tmp_path / f"{model}.json"), model, nx, nu, 2000, N, model=model)
+    s = mmpc_mod.Solver(p)
+    m = mmpc_mod.MultiSolver(p, [0, 0])
+    L = s._L
+    x0, up, tr, _, V, _ = _arrays(nx, nu, N, B, s.NV)
+    w = np.ones((B, nx + 2 * nu))
+    lb, ub = -np.ones(nu), np.ones(nu)
+    pre = (B, a(x0), a(up), a(tr), a(w))
+    for ws in (-1, 1, nx + 2 * nu - 1):
+        calls = {
+            "mmpc_solve_batch_bounds": (s._h, *pre, ws, a(lb), a(ub), 0, a(V), None, None, None, None, None),
+            "mmpc_solve_batch_pinned": (s._h, *pre, ws, a(lb), a(ub), 0, None, 0, a(V), None, None, None, None, None),
+            "mmpc_solve_batch_host_pinned": (s._h, *pre, ws, a(lb), a(ub), 0, None, 0, a(V), None, None, None),
+            "mmpc_multi_solve_batch_host_pinned": (m._m, *pre, ws, a(lb), a(ub), 0, None, 0, a(V), None, None, None),
+            "mmpc_multi_solve_batch_rccl_bounds": (m._m, *pre, ws, a(lb), a(ub), 0, a(V), None, None, None, None),
+        }
+        for fn, args in calls.items():
+            rc = getattr(L, fn)(*args)
+            assert rc == -1, (fn, ws, rc, L.mmpc_last_error())
+            assert "weights_stride" in L.mmpc_last_error().decode(), (fn, ws, L.mmpc_last_error())
+    s.close()
     m.close()
 
 
