@@ -341,6 +341,70 @@ int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, co
                                  const double* u_lb, const double* u_ub, int64_t bounds_stride, const double* u_pin,
                                  int32_t n_pin, double* V_inout, int32_t* status, int32_t* iters, double* kkt_res);
 
+/* ---- feedback gains along the plan (additive to ABI 6) ----
+ * A solve returns an open-loop plan: V*, published by the reference as control_results[i] = (time_i, x_est_i, u_i) and
+ * read through ModelControl::control_at_time (ModelControl.cpp:174-197).  When the plant is not at x_est_i when u_i is
+ * applied, the published control is off by (d u_i / d x_i) (x - x_est_i).  These entry points return the quantity that repairs it
+ * to first order, the time-varying feedback gain at V:  u_i + G_i[:, :nx] (x_meas - x_est_i)  is the
+ * neighbouring-extremal control (what RTI-style MPC applies between solves).
+ *
+ * Definition.  Take the tail problem from stage k: the stages k..N-1 of the NLP of ModelGenerator.cpp:191-222, from
+ * x_k = x with u_{k-1} = v.  G_k in R^{nu x (nx+nu)} is d u_k / d(x, v) of its solution at (x_k*, u*_{k-1}), with
+ * u*_{-1} = u_prev; by optimality the solution of the tail problem there is the plan's own tail.  With s = (dx, dv),
+ * K = nx + nu and P_N = 0 (K x K), the recursion runs backward over k = N-1..0:
+ *   A_k = I + h f_x, B_k = h f_u, e_k = F(x_k, u_k) - r_k;
+ *   nu_k = 2 Q e_k + lam_k, with lam_{N-1} = 0 and lam_{k-1} = A_k^T nu_k (the multipliers of the defects);
+ *   S_k = 2 [A_k|B_k]^T Q [A_k|B_k] on (x_k, u_k); with the exact Hessian, plus W_k = sum_r h nu_k[r] d^2 f_r/d(x,u)^2
+ *   (the dynamics part of nlp_hess_l, ModelGenerator.cpp:238, as mmpc_nlp_hess_batch forms it);
+ *   M = T^T P_{k+1} T + S_k placed on (dx, du) + 2R [[I, -I], [-I, I]] on (dv, du) + 2Rm on (du, du), where T maps
+ *   (dx, dv, du) to s' = (A_k dx + B_k du, du).  The Delta-u term's further +2R on u_k for k + 1 < N (in
+ *   mmpc_nlp_hess_batch's block) arrives through P_{k+1} and is not added twice;
+ *   G_k = -M_uu^-1 M_us and P_k = M_ss - M_su M_uu^-1 M_us.
+ * A control counts as held when u_k[c] equals its lower or upper bound bit for bit (the projected SQP returns exact
+ * bound values; |b| >= 1e19 is infinite) or when k < n_pin (the committed controls of mmpc_solve_batch_pinned).  For a
+ * held control its row and column of M_uu become identity, its row of M_us becomes zero, and G_k's row is exactly 0.
+ * M_uu on the free controls is factorised by Cholesky.  A pivot that is <= 0 or non-finite at any stage under the exact
+ * Hessian redoes the whole instance with Gauss-Newton, so no instance gets mixed Hessians.  Per instance:
+ *   gain_status 0   as asked
+ *               1   Gauss-Newton fallback
+ *               2   failed (non-finite input, or not positive definite even with Gauss-Newton): all gains are written
+ *                   as 0, i.e. pure feed-forward; neighbours in the batch are untouched
+ * V need not be a solution: the gains are those of the quadratic model at the V given.
+ *
+ * Arguments.  V [B][NV], u_prev, traj, weights / weights_stride as for the solves.  u_lb, u_ub, bounds_stride follow
+ * the mmpc_solve_batch_bounds rules exactly, stride validation included (either pointer may be NULL).
+ *   n_pin     0 .. N - 1: stages k < n_pin are held.
+ *   n_gain    1 .. N: the sweep always runs all N stages, n_gain only limits what is written.
+ *   G_out     [B][n_gain][nu][nx+nu] row-major; columns 0..nx-1 are d u_k / d x_k, columns nx.. are d u_k / d u_{k-1}.
+ *   hessian   enum mmpc_hessian.  AUTO means EXACT wherever the model has second derivatives -- the true derivative is
+ *             wanted whatever Hessian the solve ran, so this is NOT mmpc_resolve_hessian.  GAUSS_NEWTON gives the
+ *             iLQR / RTI gain.  EXACT on a model without second derivatives: MMPC_ERR_UNSUPPORTED.
+ *   kernel    enum mmpc_gain_kernel.  LANE: one lane per instance, a single fused backward sweep without any workspace.
+ *             GROUP: 16 lanes per instance (stage-parallel model evaluations, column j of the Riccati matrices on lane
+ *             j), needs nx + nu < 16 and one instance's stage records within 160 KB of LDS -- MMPC_ERR_UNSUPPORTED
+ *             otherwise.  AUTO: GROUP where it is available and its workgroups (up to 4 instances each, fewer when the
+ *             LDS admits fewer) are at most two per compute unit, else LANE (measured).  The two kernels
+ *             run the same operations per instance and agree to rounding, not bit for bit.
+ *   gain_status   [B] or NULL.
+ * Refused with MMPC_ERR_UNSUPPORTED, never run under another meaning: a linear-mode model; a handle with any finite
+ * state bound (barrier-smoothed sensitivities are another feature).  n_gain outside 1..N, n_pin outside 0..N-1, a bad
+ * bounds_stride, an unknown hessian or kernel: MMPC_ERR_INVALID_ARG, mmpc_last_error names the argument.  Everything is
+ * checked from the arguments alone before any device call; B = 0 is a no-op success.
+ * mmpc_feedback_gains_batch takes DEVICE pointers, is stream-ordered on `stream`, never synchronises and never
+ * allocates: neither kernel uses the handle's workspace (mmpc_reserve_workspace's sizes do not include anything for
+ * it), so a gain launch can be captured in a hipGraph.  mmpc_feedback_gains_batch_host takes host pointers and is
+ * synchronous.  Multi-device and RCCL entries: out of scope. */
+enum mmpc_gain_kernel { MMPC_GAIN_KERNEL_AUTO = 0, MMPC_GAIN_KERNEL_LANE = 1, MMPC_GAIN_KERNEL_GROUP = 2 };
+int mmpc_feedback_gains_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, int32_t n_gain, int32_t hessian, int32_t kernel,
+                              double* G_out, int32_t* gain_status, void* stream);
+int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev,
+                                   const double* traj, const double* weights, int64_t weights_stride,
+                                   const double* u_lb, const double* u_ub, int64_t bounds_stride, int32_t n_pin,
+                                   int32_t n_gain, int32_t hessian, int32_t kernel, double* G_out,
+                                   int32_t* gain_status);
+
 /* Continuous-time linearisation at (x[b], u[b]): A = df/dx [nx*nx], B = df/du [nx*nu]
  * column-major, xdot = f(x,u) [nx].  DEVICE pointers; any output may be NULL. */
 int mmpc_linearize_batch(mmpc_handle* h, int64_t B, const double* x, const double* u,

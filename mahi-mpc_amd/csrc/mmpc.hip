@@ -24,6 +24,7 @@
 
 #include "../../include/mmpc.h"
 #include "json_lite.h"
+#include "gain_sweep.h"
 #include "group_launch.h"
 #include "lane_launch.h"
 #include "models.h"
@@ -97,13 +98,17 @@ struct DeviceGuard {
     int prev = -1;
     bool changed = false;
     int err = 0;
+    // A failed call here is reported by the entry point (MMPC_ERR_NO_DEVICE); HIP also keeps it as the thread's last
+    // error, where the hipGetLastError() after a later, healthy kernel launch of this thread would find it: cleared.
     explicit DeviceGuard(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) {
+            (void)hipGetLastError();
             err = 1;
             return;
         }
         if (dev >= 0 && dev != prev) {
             if (hipSetDevice(dev) != hipSuccess) {
+                (void)hipGetLastError();
                 err = 1;
                 return;
             }
@@ -1278,6 +1283,145 @@ int ensure_host_ctx(mmpc_handle* h, size_t bytes) {
     return MMPC_OK;
 }
 
+// ---- feedback gains (mmpc_feedback_gains_batch; gain_sweep.h) ----
+struct GainArgs {
+    int64_t B = 0;
+    const double *V = nullptr, *u_prev = nullptr, *traj = nullptr, *weights = nullptr;
+    int64_t weights_stride = 0;
+    const double *u_lb = nullptr, *u_ub = nullptr;
+    int64_t bounds_stride = 0;
+    int32_t n_pin = 0, n_gain = 0, hessian = 0, kernel = 0;
+    double* G = nullptr;
+    int32_t* status = nullptr;
+    hipStream_t stream = nullptr;
+};
+// instances per workgroup of the 16-lane gain kernel: as many as fit 160 KB of LDS, 0 when one does not
+int gain_group_gpw(const mmpc_model_info& mi, bool exact) {
+    const size_t inst = static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, exact)) *
+                        sizeof(double);
+    return static_cast<int>(std::min<size_t>(kGroupsPerWave, kMaxGroupLds / inst));
+}
+// The one check of a gain call's arguments: pure arithmetic on the arguments and the handle, before any device call.
+// *exact: the Hessian the call runs (AUTO: exact wherever the model has second derivatives -- the true derivative is
+// wanted whatever Hessian the solve ran, so this is not resolve_hessian).
+int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    const mmpc_model_info& mi = h->info;
+    const int N = mi.num_shooting_nodes;
+    if (a.n_pin < 0 || a.n_pin > N - 1)
+        return fail(MMPC_ERR_INVALID_ARG, "n_pin must be 0 .. N - 1 (" + std::to_string(N - 1) + "), got " +
+                                              std::to_string(a.n_pin));
+    if (a.n_gain < 1 || a.n_gain > N)
+        return fail(MMPC_ERR_INVALID_ARG, "n_gain must be 1 .. N (" + std::to_string(N) + "), got " +
+                                              std::to_string(a.n_gain));
+    if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(mi, a.bounds_stride)) return rc;
+    if (a.hessian < MMPC_HESSIAN_AUTO || a.hessian > MMPC_HESSIAN_EXACT)
+        return fail(MMPC_ERR_INVALID_ARG, "hessian: not an mmpc_hessian value (" + std::to_string(a.hessian) + ")");
+    if (a.kernel < MMPC_GAIN_KERNEL_AUTO || a.kernel > MMPC_GAIN_KERNEL_GROUP)
+        return fail(MMPC_ERR_INVALID_ARG, "kernel: not an mmpc_gain_kernel value (" + std::to_string(a.kernel) + ")");
+    if (mi.is_linear)
+        return fail(MMPC_ERR_UNSUPPORTED, "feedback gains are not available for a linear-mode model");
+    {
+        std::lock_guard<std::mutex> lk(h->xb_mu);
+        if (h->x_bounded)
+            return fail(MMPC_ERR_UNSUPPORTED, "feedback gains are not available with finite state bounds "
+                                              "(barrier-smoothed sensitivities are not computed)");
+    }
+    bool has_hess = false;
+    with_model(mi.model_id, [&](auto* m) {
+        has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
+        return MMPC_OK;
+    });
+    if (a.hessian == MMPC_HESSIAN_EXACT && !has_hess)
+        return fail(MMPC_ERR_UNSUPPORTED, "hessian = EXACT: the model has no second derivatives");
+    *exact = a.hessian != MMPC_HESSIAN_GAUSS_NEWTON && has_hess;
+    if (a.kernel == MMPC_GAIN_KERNEL_GROUP) {
+        if (mi.num_x + mi.num_u >= kGroupLanes)
+            return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel) needs nx + nu < 16");
+        if (gain_group_gpw(mi, *exact) < 1)
+            return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel): the stage records of one instance "
+                                              "exceed 160 KB of LDS at this horizon");
+    }
+    if (a.B == 0) return MMPC_OK;
+    if (!a.V || !a.u_prev || !a.traj || !a.weights) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
+    if (!a.G) return fail(MMPC_ERR_INVALID_ARG, "G_out is NULL");
+    if (a.weights_stride != 0 && a.weights_stride < mi.num_x + 2 * mi.num_u)
+        return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
+    if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
+    return MMPC_OK;
+}
+// The kernel a gain call of B instances runs (measured on one MI355X, tools/feedback_gains_cost.py): the
+// 16-lane kernel while its workgroups are at most two per compute unit -- B <= 2 gpw CUs, gpw = the instances per
+// workgroup the LDS admits -- where the model has nx + nu < 16 and an instance's records fit the LDS; one lane per
+// instance beyond.  The two kernels cross between two and four workgroups per CU on both built-in models (cfg#2 shape:
+// 59 against 68 us at B = 2048, 118 against 69 at 4096; exo N = 50, one instance per workgroup: 0.30 against 1.07 ms at
+// B = 256, 1.21 against 1.08 at 1024): the lane kernel's time is flat in B up to 16384 instances, the 16-lane kernel's
+// grows with the workgroups a CU has to take.  (The first rule, 16 B lanes within four waves per SIMD, was B <= 64 per
+// CU.)
+int resolve_gain_kernel(const mmpc_handle* h, int64_t B, bool exact, int kernel) {
+    if (kernel != MMPC_GAIN_KERNEL_AUTO) return kernel;
+    const mmpc_model_info& mi = h->info;
+    const int gpw = mi.num_x + mi.num_u < kGroupLanes ? gain_group_gpw(mi, exact) : 0;
+    return gpw >= 1 && B <= 2LL * gpw * h->cu_count ? MMPC_GAIN_KERNEL_GROUP : MMPC_GAIN_KERNEL_LANE;
+}
+template <class M, bool EXACT, bool BOUNDED>
+int launch_gain_kernels(int kernel, const GainParams& p, size_t lds, hipStream_t stream) {
+    if (kernel == MMPC_GAIN_KERNEL_LANE) {
+        gain_lane_kernel<M, EXACT, BOUNDED><<<grid1d(p.B, 64), 64, 0, stream>>>(p);
+    } else if constexpr (M::NX + M::NU < kGroupLanes) {
+        auto* const k = &gain_group_kernel<M, EXACT, BOUNDED>;
+        if (lds > 64 * 1024)   // gfx950: up to 160 KB per workgroup once the attribute is raised
+            MMPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         static_cast<int>(lds)));
+        k<<<grid1d(p.B, p.gpw), 64, lds, stream>>>(p);
+    } else {
+        return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel) needs nx + nu < 16");
+    }
+    MMPC_HIP(hipGetLastError());
+    return MMPC_OK;
+}
+// a gain call whose arguments check_gain_args has passed, B > 0, device pointers, on the current device: one launch,
+// stream-ordered, no allocation, no synchronisation
+int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact) {
+    const mmpc_model_info& mi = h->info;
+    if (a.kernel == MMPC_GAIN_KERNEL_AUTO)
+        if (int rc = query_cu_count(h)) return rc;
+    const int kernel = resolve_gain_kernel(h, a.B, exact, a.kernel);
+    GainParams p{};
+    p.B = a.B;
+    p.N = mi.num_shooting_nodes;
+    p.h = mi.step_size;
+    p.V = a.V;
+    p.u_prev = a.u_prev;
+    p.traj = a.traj;
+    p.weights = a.weights;
+    p.w_stride = a.weights_stride;
+    p.u_lb = a.u_lb;
+    p.u_ub = a.u_ub;
+    p.b_stride = static_cast<int32_t>(a.bounds_stride);
+    p.n_pin = a.n_pin;
+    p.n_gain = a.n_gain;
+    p.G = a.G;
+    p.status = a.status;
+    p.gpw = kernel == MMPC_GAIN_KERNEL_GROUP ? gain_group_gpw(mi, exact) : 1;
+    const size_t lds = kernel == MMPC_GAIN_KERNEL_GROUP
+                           ? static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, p.N, exact)) * p.gpw *
+                                 sizeof(double)
+                           : 0;
+    const bool bounded = a.u_lb || a.u_ub;
+    return with_model(mi.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        if constexpr (HasHess<M>::value) {
+            if (exact)
+                return bounded ? launch_gain_kernels<M, true, true>(kernel, p, lds, a.stream)
+                               : launch_gain_kernels<M, true, false>(kernel, p, lds, a.stream);
+        }
+        return bounded ? launch_gain_kernels<M, false, true>(kernel, p, lds, a.stream)
+                       : launch_gain_kernels<M, false, false>(kernel, p, lds, a.stream);
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -1574,6 +1718,75 @@ int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, co
     if (status) MMPC_HIP(hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (iters) MMPC_HIP(hipMemcpyAsync(iters, dit, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (kkt_res) MMPC_HIP(hipMemcpyAsync(kkt_res, d + off_kkt, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    MMPC_HIP(hipStreamSynchronize(s));
+    return MMPC_OK;
+}
+
+int mmpc_feedback_gains_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, int32_t n_gain, int32_t hessian, int32_t kernel,
+                              double* G_out, int32_t* gain_status, void* stream) {
+    const GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian,
+                     kernel, G_out, gain_status, reinterpret_cast<hipStream_t>(stream)};
+    bool exact = false;
+    if (int rc = check_gain_args(h, a, &exact)) return rc;
+    if (B == 0) return MMPC_OK;
+    int dev;
+    int rc = resolve_device(h, &dev);
+    if (rc) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    return launch_gains(h, a, exact);
+}
+
+int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev,
+                                   const double* traj, const double* weights, int64_t weights_stride,
+                                   const double* u_lb, const double* u_ub, int64_t bounds_stride, int32_t n_pin,
+                                   int32_t n_gain, int32_t hessian, int32_t kernel, double* G_out,
+                                   int32_t* gain_status) {
+    GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian, kernel,
+               G_out, gain_status};
+    bool exact = false;
+    if (int rc = check_gain_args(h, a, &exact)) return rc;   // before weights_stride and bounds_stride size a copy
+    if (B == 0) return MMPC_OK;
+    std::lock_guard<std::mutex> lk(h->host_mu);
+    const mmpc_model_info& mi = h->info;
+    const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
+    const size_t nW = weights_stride ? static_cast<size_t>(B) * static_cast<size_t>(weights_stride) : nx + 2 * nu;
+    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
+    const size_t nB = (bounds_stride ? static_cast<size_t>(B) - 1 : 0) * static_cast<size_t>(bounds_stride) + nu;
+    const size_t nG = static_cast<size_t>(B) * static_cast<size_t>(n_gain) * nu * (nx + nu);
+    const size_t off_V = 0, off_up = off_V + B * NV, off_tr = off_up + B * nu, off_w = off_tr + B * N * nx;
+    const size_t off_lb = off_w + nW, off_ub = off_lb + nB, off_G = off_ub + nB, off_st = off_G + nG;
+    const size_t total = off_st + (B + 1) / 2;
+    int dev;
+    int rc = resolve_device(h, &dev);
+    if (rc) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    rc = ensure_host_ctx(h, total * sizeof(double));
+    if (rc) return rc;
+    double* d = h->d_buf;
+    hipStream_t s = h->host_stream;
+    MMPC_HIP(hipMemcpyAsync(d + off_V, V, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_up, u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_tr, traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_w, weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
+    a.V = d + off_V;
+    a.u_prev = d + off_up;
+    a.traj = d + off_tr;
+    a.weights = d + off_w;
+    a.u_lb = u_lb ? d + off_lb : nullptr;
+    a.u_ub = u_ub ? d + off_ub : nullptr;
+    a.G = d + off_G;
+    a.status = dst;
+    a.stream = s;
+    if ((rc = launch_gains(h, a, exact))) return rc;
+    MMPC_HIP(hipMemcpyAsync(G_out, d + off_G, nG * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (gain_status) MMPC_HIP(hipMemcpyAsync(gain_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MMPC_HIP(hipStreamSynchronize(s));
     return MMPC_OK;
 }

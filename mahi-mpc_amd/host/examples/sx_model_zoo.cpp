@@ -4,6 +4,9 @@
 //   cart_pole       x = [p, th, p_dot, th_dot], u = [F]       second order, nq = 2 (tanh friction, division)
 //   unicycle        x = [px, py, th, v],        u = [a, w]    first order,  nq = 0 (sqrt drag)
 //   motor_pendulum  x = [th, om, i],            u = [V]       mixed,        nq = 1, na = 2 (exp, sq)
+// and one model at the width limit of the 16-lane kernels (nx + nu = 16: one lane per column no longer fits):
+//   mass_chain      x = [p0..p5, v0..v5],       u = [f0..f3]  second order, nq = 6: six masses in a row coupled by
+//                   sinusoidal springs, forces on masses 0, 2, 3 and 5
 // The same equations are restated in sympy in tests/test_sx_models.py.
 //   sx_model_zoo <model> <N> [linear]      writes <model>{,_model.h,_linear_functions.{c,so},.so,.json} in the cwd
 #include <Mahi/Mpc.hpp>
@@ -12,13 +15,14 @@
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <vector>
 
 using namespace casadi;
 using namespace mahi::mpc;
 
 int main(int argc, char* argv[]) {
     if (argc < 3) {
-        std::cerr << "usage: sx_model_zoo cart_pole|unicycle|motor_pendulum N [linear]" << std::endl;
+        std::cerr << "usage: sx_model_zoo cart_pole|unicycle|motor_pendulum|mass_chain N [linear]" << std::endl;
         return 2;
     }
     const std::string which = argv[1];
@@ -49,6 +53,25 @@ int main(int argc, char* argv[]) {
         x = SX::vertcat({th, om, i});
         x_dot = SX::vertcat({om, om_dot, i_dot});
         u = V;
+    } else if (which == "mass_chain") {
+        std::vector<SX> p, v, f, xs, xd;
+        for (int i = 0; i < 6; ++i) p.push_back(SX::sym("p" + std::to_string(i)));
+        for (int i = 0; i < 6; ++i) v.push_back(SX::sym("v" + std::to_string(i)));
+        for (int i = 0; i < 4; ++i) f.push_back(SX::sym("f" + std::to_string(i)));
+        const int actuator[6] = {0, -1, 1, 2, -1, 3};
+        xs = p;
+        xs.insert(xs.end(), v.begin(), v.end());
+        xd = v;
+        for (int i = 0; i < 6; ++i) {
+            SX a = -0.3 * v[i] - 2.0 * sin(p[i]);
+            if (i > 0) a = a + 5.0 * sin(p[i - 1] - p[i]);
+            if (i < 5) a = a + 5.0 * sin(p[i + 1] - p[i]);
+            if (actuator[i] >= 0) a = a + f[actuator[i]];
+            xd.push_back(a);
+        }
+        x = SX::vertcat(xs);
+        x_dot = SX::vertcat(xd);
+        u = SX::vertcat(f);
     } else {
         std::cerr << "unknown model " << which << std::endl;
         return 2;

@@ -87,6 +87,18 @@ public:
     // applying.  The [B][m][nu] table is packed into the tick's staging slot and travels in its single H2D
     // (mmpc_solve_batch_pinned).  m = 0 (default) pins nothing; m must be 0 .. N - 1.  Additive.
     void set_num_control_inputs_saved(int m);
+    // Feedback along the plans (ModelControl::set_feedback_stages for every controller of the batch; include/mmpc.h,
+    // "feedback gains"): the gain launch goes onto the tick's stream behind the solve, under that tick's limits and
+    // pins, and the gains of the first n stages travel in the slot's download with the solution.  n must be 0 .. N; 0
+    // (the default) launches nothing and every published value is what it is without this call.  Additive.
+    void set_feedback_stages(int n);
+    // G_i of instance b's published plan, num_u x (num_x + num_u) row-major, and the instances' gain status (0 as
+    // asked, 1 Gauss-Newton fallback, 2 failed: gains 0; empty when the published tick carries no gains)
+    std::vector<double> feedback_gain(int64_t b, int i);
+    std::vector<int> feedback_status();
+    // controls_at_time with the measured states [B*nx]: per instance clamp(u_i + G_i[:, :nx] (x_measured - x_est_i),
+    // u_min, u_max) with that instance's limits; the plan for a stage without gains or an instance with status 2
+    std::vector<double> controls_at_time(mahi::util::Time time, const std::vector<double>& states_measured);
 
 private:
     struct Impl;
@@ -108,6 +120,10 @@ private:
     mahi::util::Time m_out_time;
     std::vector<double> m_out_V;
     std::vector<int> m_out_status, m_out_iters;
+    int m_out_fb = 0;                 // stages the published tick carries gains for
+    std::vector<double> m_out_G;      // [B][m_out_fb][nu][nx + nu]
+    std::vector<int> m_out_gst;       // [B]
+    std::atomic<int> m_feedback_stages{0};
 
     std::mutex m_weights_mutex;
     std::vector<double> m_Q, m_R, m_Rm;

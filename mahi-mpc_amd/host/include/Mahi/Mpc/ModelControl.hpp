@@ -72,6 +72,23 @@ public:
     // before solving.  m = 0 (the default) is the reference's behaviour; m must be 0 .. N - 1; linear-mode models
     // throw at the first pinned solve.  Additive: not part of the reference's interface.
     void set_num_control_inputs_saved(int m);
+    // Feedback along the plan (include/mmpc.h, "feedback gains"): after each solve the gains G_i = d u_i* / d(x_i,
+    // u_{i-1}) of the first n stages are computed from the published V*, under the control limits in force (a control
+    // on a limit has a zero row) and with the committed controls of that solve held, and published with the plan.
+    // n must be 0 .. N; 0 (the default) computes nothing, and every published value is what it is without this call.
+    // A linear-mode model or finite state bounds make the next calc_u throw.  Additive: not part of the reference's
+    // interface (ModelControl.cpp:174-197 publishes and reads the open-loop plan only).
+    void set_feedback_stages(int n);
+    // G_i of the published plan, num_u x (num_x + num_u) row-major (columns 0 .. num_x - 1: d u_i / d x_i); i must be
+    // below the number of stages the published plan carries gains for
+    std::vector<double> feedback_gain(int i);
+    // 0 as asked (the exact Hessian where the model has second derivatives), 1 Gauss-Newton fallback, 2 failed (the
+    // gains are 0: pure feed-forward); -1 when the published plan carries no gains
+    int feedback_status();
+    // control_at_time with the measured state: the stage i of the reference's index rule (ModelControl.cpp:192-197),
+    // and ControlResult{time_i, x_est_i, clamp(u_i + G_i[:, :nx] (x_measured - x_est_i), u_min, u_max)} -- the
+    // neighbouring-extremal control.  For a stage without gains (i >= n, or feedback_status() == 2): the plan.
+    ControlResult control_at_time(mahi::util::Time time, const std::vector<double>& x_measured);
 
     // ---- build extensions (not in the reference) ----
     // solver status of the last calc_u (the reference ignores IPOPT's status, ModelControl.cpp:159-161)
@@ -114,12 +131,15 @@ private:
     std::mutex m_weights_mutex;
 
     std::atomic<int> m_num_control_inputs_saved{0};  // ModelControl.hpp:79 (there an int without a setter)
+    std::atomic<int> m_feedback_stages{0};
+    std::vector<double> m_gains;   // [n][nu][nx + nu] of the published plan (under m_output_mutex, as m_gain_status)
+    int m_gain_status = -1;
 
     int m_last_status = -1;
     int m_last_iters = 0;
     double m_last_kkt = 0.0;
 
-    void format_outputs(const std::vector<double>& opt_output);
+    void format_outputs(const std::vector<double>& opt_output, std::vector<double> gains = {}, int gain_status = -1);
     std::vector<double> packed_weights();
     // calc_u_batch with this object's limits (u_mins == nullptr) or a row of limits per instance
     std::vector<std::vector<double>> calc_u_batch_impl(const std::vector<std::vector<double>>& states,

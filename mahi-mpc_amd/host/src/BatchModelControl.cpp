@@ -50,6 +50,13 @@ struct BatchModelControl::Impl {
     double* h_V[2] = {nullptr, nullptr};
     int32_t* h_st[2] = {nullptr, nullptr};
     int32_t* h_it[2] = {nullptr, nullptr};
+    // feedback gains (set_feedback_stages): per-slot device and pinned host buffers for N stages, allocated at the
+    // first call that turns feedback on; fb[slot] = stages the slot's tick computed
+    double* d_G[2] = {nullptr, nullptr};
+    double* h_G[2] = {nullptr, nullptr};
+    int32_t* d_gst[2] = {nullptr, nullptr};
+    int32_t* h_gst[2] = {nullptr, nullptr};
+    int fb[2] = {0, 0};
     hipEvent_t h2d_done[2] = {nullptr, nullptr}, solved[2] = {nullptr, nullptr}, d2h_done[2] = {nullptr, nullptr};
     bool pending[2] = {false, false};
     mahi::util::Time pend_time[2];
@@ -140,6 +147,10 @@ BatchModelControl::~BatchModelControl() {
         (void)hipHostFree(m->h_V[s]);
         (void)hipHostFree(m->h_st[s]);
         (void)hipHostFree(m->h_it[s]);
+        (void)hipFree(m->d_G[s]);
+        (void)hipHostFree(m->h_G[s]);
+        (void)hipFree(m->d_gst[s]);
+        (void)hipHostFree(m->h_gst[s]);
         if (m->h2d_done[s]) (void)hipEventDestroy(m->h2d_done[s]);
         if (m->solved[s]) (void)hipEventDestroy(m->solved[s]);
         if (m->d2h_done[s]) (void)hipEventDestroy(m->d2h_done[s]);
@@ -239,6 +250,15 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
                                           per_instance ? static_cast<int64_t>(nu) : 0, d + off_pin, n_pin, I.d_V,
                                           I.d_st[slot], I.d_it[slot], nullptr, nullptr, I.compute),
                 "mmpc_solve_batch_pinned");
+    // feedback gains at the solution, behind the solve on the tick's stream, with the tick's limits and pins
+    const int n_fb = m_feedback_stages.load();
+    I.fb[slot] = n_fb;
+    if (n_fb > 0)
+        I.check(I.lib->feedback_gains_batch(I.h, I.B, I.d_V, d + I.off_up, d + I.off_tr, d + I.off_w, 0,
+                                            finite ? d + olb : nullptr, finite ? d + oub : nullptr,
+                                            per_instance ? static_cast<int64_t>(nu) : 0, n_pin, n_fb, MMPC_HESSIAN_AUTO,
+                                            MMPC_GAIN_KERNEL_AUTO, I.d_G[slot], I.d_gst[slot], I.compute),
+                "mmpc_feedback_gains_batch");
     // the next solve updates d_V in place: download from a per-slot copy
     HIPC(hipMemcpyAsync(I.d_Vout[slot], I.d_V, b * NV * sizeof(double), hipMemcpyDeviceToDevice, I.compute));
     HIPC(hipEventRecord(I.solved[slot], I.compute));
@@ -246,6 +266,11 @@ void BatchModelControl::enqueue_tick(int slot, mahi::util::Time time, const doub
     HIPC(hipMemcpyAsync(I.h_V[slot], I.d_Vout[slot], b * NV * sizeof(double), hipMemcpyDeviceToHost, I.copy));
     HIPC(hipMemcpyAsync(I.h_st[slot], I.d_st[slot], b * sizeof(int32_t), hipMemcpyDeviceToHost, I.copy));
     HIPC(hipMemcpyAsync(I.h_it[slot], I.d_it[slot], b * sizeof(int32_t), hipMemcpyDeviceToHost, I.copy));
+    if (n_fb > 0) {   // the gains travel in the slot's download with the solution
+        HIPC(hipMemcpyAsync(I.h_G[slot], I.d_G[slot], b * n_fb * nu * (nx + nu) * sizeof(double), hipMemcpyDeviceToHost,
+                            I.copy));
+        HIPC(hipMemcpyAsync(I.h_gst[slot], I.d_gst[slot], b * sizeof(int32_t), hipMemcpyDeviceToHost, I.copy));
+    }
     HIPC(hipEventRecord(I.d2h_done[slot], I.copy));
     I.pending[slot] = true;
     I.pend_time[slot] = time;
@@ -264,6 +289,14 @@ void BatchModelControl::publish(int slot) {
             m_out_iters[i] = I.h_it[slot][i];
         }
         m_out_time = I.pend_time[slot];
+        m_out_fb = I.fb[slot];
+        if (m_out_fb > 0) {
+            m_out_G.assign(I.h_G[slot], I.h_G[slot] + b * m_out_fb * I.nu * (I.nx + I.nu));
+            m_out_gst.assign(I.h_gst[slot], I.h_gst[slot] + b);
+        } else {
+            m_out_G.clear();
+            m_out_gst.clear();
+        }
     }
     m_tick_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - I.pend_t0[slot]).count();
     I.pending[slot] = false;
@@ -363,6 +396,77 @@ std::vector<double> BatchModelControl::controls_at_time(mahi::util::Time time) {
         out.insert(out.end(), r.u.begin(), r.u.end());
     }
     return out;
+}
+
+std::vector<double> BatchModelControl::controls_at_time(mahi::util::Time time, const std::vector<double>& states_measured) {
+    const size_t nx = m->nx, nu = m->nu, K = nx + nu, N = m->N, B = static_cast<size_t>(m_B);
+    if (states_measured.size() != B * nx)
+        throw std::invalid_argument("controls_at_time: states_measured must have B * num_x entries");
+    std::vector<double> lo(B * nu, -INFINITY), hi(B * nu, INFINITY);
+    {
+        std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+        for (size_t b = 0; b < B; ++b)
+            for (size_t c = 0; c < nu; ++c) {
+                if (m_limits_per_instance) {
+                    lo[b * nu + c] = m_u_min_table[b * nu + c];
+                    hi[b * nu + c] = m_u_max_table[b * nu + c];
+                } else {
+                    if (c < model_parameters.u_min.size()) lo[b * nu + c] = model_parameters.u_min[c];
+                    if (c < model_parameters.u_max.size()) hi[b * nu + c] = model_parameters.u_max[c];
+                }
+            }
+    }
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    if (m_ticks == 0) throw std::logic_error("controls_at_time before the first solve");
+    size_t i = 0;   // ModelControl.cpp:192-197
+    while (i < N && mahi::util::seconds(m_out_time.as_seconds() + m->step * i) < time) i++;
+    const size_t k = i == 0 ? 0 : i - 1;
+    std::vector<double> out(B * nu);
+    for (size_t b = 0; b < B; ++b) {
+        const double* v = m_out_V.data() + b * m->NV + k * K;
+        const bool fb = k < static_cast<size_t>(m_out_fb) && m_out_gst[b] != 2;
+        const double* G = fb ? m_out_G.data() + (b * m_out_fb + k) * nu * K : nullptr;
+        for (size_t c = 0; c < nu; ++c) {
+            double u = v[nx + c];
+            if (fb) {
+                for (size_t j = 0; j < nx; ++j) u += G[c * K + j] * (states_measured[b * nx + j] - v[j]);
+                u = std::min(std::max(u, lo[b * nu + c]), hi[b * nu + c]);
+            }
+            out[b * nu + c] = u;
+        }
+    }
+    return out;
+}
+
+void BatchModelControl::set_feedback_stages(int n) {
+    if (n < 0 || n > m->N) throw std::invalid_argument("set_feedback_stages: n must be 0 .. num_shooting_nodes");
+    std::lock_guard<std::mutex> lg(m_solve_mutex);   // between ticks
+    Impl& I = *m;
+    if (n > 0 && !I.d_G[0]) {
+        HIPC(hipSetDevice(I.dev));
+        const size_t g = static_cast<size_t>(I.B) * I.N * I.nu * (I.nx + I.nu) * sizeof(double);
+        for (int s = 0; s < 2; ++s) {
+            HIPC(hipMalloc(reinterpret_cast<void**>(&I.d_G[s]), g));
+            HIPC(hipHostMalloc(reinterpret_cast<void**>(&I.h_G[s]), g, hipHostMallocDefault));
+            HIPC(hipMalloc(reinterpret_cast<void**>(&I.d_gst[s]), I.B * sizeof(int32_t)));
+            HIPC(hipHostMalloc(reinterpret_cast<void**>(&I.h_gst[s]), I.B * sizeof(int32_t), hipHostMallocDefault));
+        }
+    }
+    m_feedback_stages = n;
+}
+
+std::vector<double> BatchModelControl::feedback_gain(int64_t b, int i) {
+    if (b < 0 || b >= m_B) throw std::out_of_range("feedback_gain: instance index");
+    const size_t sz = static_cast<size_t>(m->nu) * (m->nx + m->nu);
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    if (i < 0 || i >= m_out_fb) throw std::out_of_range("feedback_gain: the published tick carries no gain for this stage");
+    const double* G = m_out_G.data() + (static_cast<size_t>(b) * m_out_fb + i) * sz;
+    return std::vector<double>(G, G + sz);
+}
+
+std::vector<int> BatchModelControl::feedback_status() {
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    return m_out_gst;
 }
 
 std::vector<double> BatchModelControl::solution(int64_t b) {

@@ -108,7 +108,19 @@ void ModelControl::calc_u(mahi::util::Time control_time, const std::vector<doubl
     m_last_status = st;
     m_last_iters = it;
     m_last_kkt = kkt;
-    format_outputs(m_V);  // m_V stays as the next warm start (ModelControl.cpp:160-161)
+    // feedback gains of the first n stages at the published V*, under the limits and pins of this solve
+    std::vector<double> gains;
+    int32_t gst = -1;
+    if (const int n = m_feedback_stages.load()) {
+        gains.assign(static_cast<size_t>(n) * nu * (nx + nu), 0.0);
+        m_backend->check(m_backend->feedback_gains_batch_host(
+                             m_handle, 1, m_V.data(), control.data(), traj.data(), w.data(), 0,
+                             lb.size() == nu ? lb.data() : nullptr, ub.size() == nu ? ub.data() : nullptr, 0,
+                             static_cast<int32_t>(pin.size() / nu), n, MMPC_HESSIAN_AUTO, MMPC_GAIN_KERNEL_AUTO,
+                             gains.data(), &gst),
+                         "mmpc_feedback_gains_batch_host");
+    }
+    format_outputs(m_V, std::move(gains), gst);  // m_V stays as the next warm start (ModelControl.cpp:160-161)
 }
 
 std::vector<std::vector<double>> ModelControl::calc_u_batch(const std::vector<std::vector<double>>& states,
@@ -176,7 +188,7 @@ std::vector<std::vector<double>> ModelControl::calc_u_batch_impl(const std::vect
     return out;
 }
 
-void ModelControl::format_outputs(const std::vector<double>& opt_output) {
+void ModelControl::format_outputs(const std::vector<double>& opt_output, std::vector<double> gains, int gain_status) {
     std::vector<ControlResult> local;
     const size_t nx = model_parameters.num_x, nu = model_parameters.num_u;
     for (size_t i = 0; i < static_cast<size_t>(model_parameters.num_shooting_nodes); i++) {
@@ -187,6 +199,8 @@ void ModelControl::format_outputs(const std::vector<double>& opt_output) {
     }
     std::lock_guard<std::mutex> lg(m_output_mutex);
     control_results = local;
+    m_gains = std::move(gains);   // the gains travel with their plan
+    m_gain_status = gain_status;
 }
 
 ModelControl::ControlResult ModelControl::control_at_time(mahi::util::Time time) {
@@ -196,6 +210,52 @@ ModelControl::ControlResult ModelControl::control_at_time(mahi::util::Time time)
     size_t i = 0;
     while (i < control_results.size() && control_results[i].time < time) i++;
     return (i == 0) ? control_results[0] : control_results[i - 1];
+}
+
+ModelControl::ControlResult ModelControl::control_at_time(mahi::util::Time time, const std::vector<double>& x_measured) {
+    const size_t nx = model_parameters.num_x, nu = model_parameters.num_u, K = nx + nu;
+    if (x_measured.size() != nx) throw std::invalid_argument("control_at_time: x_measured must have num_x entries");
+    std::vector<double> lo, hi;
+    {
+        std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+        lo = model_parameters.u_min;
+        hi = model_parameters.u_max;
+    }
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    if (control_results.empty()) throw std::logic_error("control_at_time before the first calc_u");
+    size_t i = 0;   // ModelControl.cpp:192-197
+    while (i < control_results.size() && control_results[i].time < time) i++;
+    if (i > 0) --i;
+    ControlResult r = control_results[i];
+    if (m_gain_status == 2 || (i + 1) * nu * K > m_gains.size()) return r;   // no gains for this stage: the plan
+    const double* G = m_gains.data() + i * nu * K;
+    for (size_t c = 0; c < nu; ++c) {
+        double u = r.u[c];
+        for (size_t j = 0; j < nx; ++j) u += G[c * K + j] * (x_measured[j] - r.x_est[j]);
+        if (lo.size() == nu) u = std::max(u, lo[c]);
+        if (hi.size() == nu) u = std::min(u, hi[c]);
+        r.u[c] = u;
+    }
+    return r;
+}
+
+void ModelControl::set_feedback_stages(int n) {
+    if (n < 0 || n > model_parameters.num_shooting_nodes)
+        throw std::invalid_argument("set_feedback_stages: n must be 0 .. num_shooting_nodes");
+    m_feedback_stages = n;
+}
+
+std::vector<double> ModelControl::feedback_gain(int i) {
+    const size_t sz = static_cast<size_t>(model_parameters.num_u) * (model_parameters.num_x + model_parameters.num_u);
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    if (i < 0 || (static_cast<size_t>(i) + 1) * sz > m_gains.size())
+        throw std::out_of_range("feedback_gain: the published plan carries no gain for this stage");
+    return std::vector<double>(m_gains.begin() + i * sz, m_gains.begin() + (i + 1) * sz);
+}
+
+int ModelControl::feedback_status() {
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    return m_gain_status;
 }
 
 void ModelControl::set_state(mahi::util::Time time, const std::vector<double>& state,

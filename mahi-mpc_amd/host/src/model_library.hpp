@@ -32,6 +32,9 @@ struct ModelLibrary {
     // committed controls (u_pin, n_pin): the mirror of set_num_control_inputs_saved
     decltype(&mmpc_solve_batch_pinned) solve_batch_pinned = &mmpc_solve_batch_pinned;
     decltype(&mmpc_solve_batch_host_pinned) solve_batch_host_pinned = &mmpc_solve_batch_host_pinned;
+    // feedback gains along the plan: the mirror of set_feedback_stages
+    decltype(&mmpc_feedback_gains_batch) feedback_gains_batch = &mmpc_feedback_gains_batch;
+    decltype(&mmpc_feedback_gains_batch_host) feedback_gains_batch_host = &mmpc_feedback_gains_batch_host;
     decltype(&mmpc_reserve_workspace) reserve_workspace = &mmpc_reserve_workspace;
     decltype(&mmpc_set_barrier_rule) set_barrier_rule = &mmpc_set_barrier_rule;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
@@ -81,6 +84,8 @@ struct ModelLibrary {
         b->bind(b->solve_batch_host_bounds, "mmpc_solve_batch_host_bounds");
         b->bind(b->solve_batch_pinned, "mmpc_solve_batch_pinned");
         b->bind(b->solve_batch_host_pinned, "mmpc_solve_batch_host_pinned");
+        b->bind(b->feedback_gains_batch, "mmpc_feedback_gains_batch");
+        b->bind(b->feedback_gains_batch_host, "mmpc_feedback_gains_batch_host");
         b->bind(b->reserve_workspace, "mmpc_reserve_workspace");
         b->bind(b->set_barrier_rule, "mmpc_set_barrier_rule");
         b->bind(b->last_error, "mmpc_last_error");

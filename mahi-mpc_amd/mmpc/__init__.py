@@ -45,6 +45,9 @@ HESSIAN_AUTO, HESSIAN_GAUSS_NEWTON, HESSIAN_EXACT = 0, 1, 2
 # barrier rule of state-bounded solves (enum mmpc_barrier_rule): IPOPT's monotone rule, or Mehrotra's
 # predictor-corrector (16-lane solver, nonlinear mode; include/mmpc.h)
 BARRIER_MONOTONE, BARRIER_MEHROTRA = 0, 1
+# kernel of the feedback-gain sweep (enum mmpc_gain_kernel) and its per-instance status
+GAIN_KERNEL_AUTO, GAIN_KERNEL_LANE, GAIN_KERNEL_GROUP = 0, 1, 2
+GAIN_OK, GAIN_GAUSS_NEWTON_FALLBACK, GAIN_FAILED = 0, 1, 2
 MODEL_TWO_LINK_ARM, MODEL_EXO_ARM, MODEL_USER = 0, 1, 2
 USER_LIB_DIR = os.path.join(ROOT, "lib", "user")
 BUILTIN_MODELS = ("two_link_arm", "double_pendulum", "exo_arm", "exo")  # "mmpc_model" names libmmpc.so serves   # models generated from SX by ModelGenerator (make -C host user)
@@ -121,6 +124,11 @@ def lib(path: str | None = None):
         L.mmpc_solve_batch_pinned.argtypes = _pin + [_vp] * 6
         L.mmpc_solve_batch_host_pinned.argtypes = _pin + [_vp] * 4
         L.mmpc_multi_solve_batch_host_pinned.argtypes = _pin + [_vp] * 4
+        # feedback gains: (V, u_prev, traj, weights), weights_stride, (u_lb, u_ub), bounds_stride, n_pin, n_gain,
+        # hessian, kernel, (G_out, gain_status[, stream])
+        _gain = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64] + [C.c_int32] * 4)
+        L.mmpc_feedback_gains_batch.argtypes = _gain + [_vp] * 3
+        L.mmpc_feedback_gains_batch_host.argtypes = _gain + [_vp] * 2
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -431,6 +439,44 @@ class Solver:
                                                          ws, _ptr(lb), _ptr(ub), bs, _ptr(V), _ptr(st), _ptr(it),
                                                          _ptr(kkt)))
         return dict(V=V, status=st, iters=it, kkt=kkt)
+
+    def feedback_gains(self, B, V, u_prev, traj, weights, G=None, gain_status=None, weights_stride=0, u_lb=None,
+                       u_ub=None, bounds_stride=0, n_pin=0, n_gain=None, hessian=HESSIAN_AUTO, kernel=GAIN_KERNEL_AUTO,
+                       stream=None):
+        """Feedback gains G_k = d u_k* / d(x_k, u_{k-1}) along the plan V (mmpc_feedback_gains_batch; device
+        pointers, stream-ordered, no allocation by the library).  Returns (G, gain_status): G [B, n_gain, nu, nx + nu]
+        (n_gain defaults to N), gain_status [B] int32 (0 as asked, 1 Gauss-Newton fallback, 2 failed: gains 0).  G and
+        gain_status are torch tensors on V's device unless given (tensors or raw addresses, returned as given)."""
+        n_gain = self.N if n_gain is None else int(n_gain)
+        if G is None or gain_status is None:
+            import torch
+            if G is None:
+                G = torch.empty((B, n_gain, self.nu, self.nx + self.nu), dtype=torch.float64, device=V.device)
+            if gain_status is None:
+                gain_status = torch.empty((B,), dtype=torch.int32, device=V.device)
+        self._check(self._L.mmpc_feedback_gains_batch(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                      weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                      int(n_pin), n_gain, int(hessian), int(kernel), _ptr(G),
+                                                      _ptr(gain_status), stream))
+        return G, gain_status
+
+    def feedback_gains_host(self, V, u_prev, traj, weights, u_lb=None, u_ub=None, n_pin=0, n_gain=None,
+                            hessian=HESSIAN_AUTO, kernel=GAIN_KERNEL_AUTO):
+        """feedback_gains for numpy arrays, synchronous (mmpc_feedback_gains_batch_host); u_lb / u_ub [nu] shared or
+        [B, nu] per instance.  Returns (G [B, n_gain, nu, nx + nu], gain_status [B])."""
+        nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
+        V = _f64(V, (-1, NV))
+        B = V.shape[0]
+        u_prev, traj, weights = _f64(u_prev, (B, nu)), _f64(traj, (B, N, nx)), _f64(weights)
+        ws = 0 if weights.ndim == 1 else weights.shape[-1]
+        n_gain = N if n_gain is None else int(n_gain)
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)
+        G = np.zeros((B, max(n_gain, 0), nu, nx + nu))
+        st = np.full(B, -1, np.int32)
+        self._check(self._L.mmpc_feedback_gains_batch_host(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj),
+                                                           _ptr(weights), ws, _ptr(lb), _ptr(ub), bs, int(n_pin),
+                                                           n_gain, int(hessian), int(kernel), _ptr(G), _ptr(st)))
+        return G, st
 
     def set_state_bounds(self, x_lb=None, x_ub=None):
         """x_lb <= x_k <= x_ub for k = 1..N (None = unbounded); finite bounds select the interior-point variant."""
