@@ -405,6 +405,71 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
                                    int32_t n_gain, int32_t hessian, int32_t kernel, double* G_out,
                                    int32_t* gain_status);
 
+/* ---- differentiable solve: reverse-mode products of the solution map (additive to ABI 6) ----
+ * V* is a function of theta = (x0, u_prev, traj, weights).  Given a cotangent V_bar [NV] these entry points return
+ * theta_bar = (d V* / d theta)^T V_bar for all of theta from one backward Riccati sweep with a vector part and one
+ * forward sweep at V -- about the cost of one SQP iteration -- where finite differences take one solve per input.
+ *
+ * Definition.  Notation as for the feedback gains above: V = (x_0, u_0, .., x_N), K = nx + nu, A_k = I + h f_x,
+ * B_k = h f_u, e_k = F(x_k, u_k) - r_k, C_k = [[A_k, B_k], [0, I]]; the stage blocks S_k (+ W_k with the exact Hessian),
+ * the multipliers nu_k, lam_k and the held mask (bit-equal to a finite bound, or k < n_pin) are those of the gains.
+ * Let z be the free entries of V (x_1..x_N and the controls not held), L = J + sum_k lam_k^T (F(x_k, u_k) - x_{k+1})
+ * and g the defects.  (a, b) solves the symmetric system
+ *     L_zz a + g_z^T b = V_bar_z,   g_z a = 0      (a = 0 on x_0 and on held controls),
+ * the equality-constrained QP min 1/2 a^T L_VV a - V_bar^T a over the linearised dynamics from a_{x,0} = 0.  With
+ * a_{x,k}, a_{u,k} its stage parts and a_{u,-1} = 0:
+ *   traj_bar[k] = 2 Q o a_{x,k+1}
+ *   Q_bar       = -2 sum_k e_k o a_{x,k+1}
+ *   R_bar       = -2 sum_k (u_k - u_{k-1}) o (a_{u,k} - a_{u,k-1}),  u_{-1} = u_prev
+ *   Rm_bar      = -2 sum_k u_k o a_{u,k}
+ *   (x0_bar | u_prev_bar) = p_0 of the recursion below: 2 R o a_{u,0} for u_prev, V_bar_{x_0} minus the stage-0 cross
+ *   terms for x0.
+ * Recursion on s = (dx_k, dv = du_{k-1}), P_N = 0, p_N = (V_bar_{x_N}; 0), backward over k = N-1..0: M_uu, M_us, M_ss
+ * and G_k exactly as in the gain definition;  q = C_k^T p_{k+1} + (V_bar_{x_k}; V_bar_{u_k});  q_u of a held control
+ * is 0;  kff_k = M_uu^-1 q_u;  p_k = (q_x; 0) + G_k^T q_u;  P_k = M_ss + M_su G_k.  Forward from s_0 = 0:
+ * a_{u,k} = G_k s_k + kff_k,  s_{k+1} = (A_k a_{x,k} + B_k a_{u,k}; a_{u,k}).
+ * V_bar entries on held controls are ignored (derivatives with respect to the bounds and the pins are another
+ * feature).  V need not be a solution: the outputs are those of the quadratic model at the V given.  Per instance:
+ *   vjp_status 0   as asked
+ *              1   Gauss-Newton fallback: a pivot <= 0 or non-finite under EXACT redoes the whole instance, both sweeps,
+ *                  with Gauss-Newton
+ *              2   failed (non-finite input, or not positive definite even with Gauss-Newton): every output row of the
+ *                  instance is written as 0; neighbours in the batch are untouched
+ *
+ * Arguments.  V, u_prev, traj, weights / weights_stride, u_lb, u_ub, bounds_stride, n_pin: as for
+ * mmpc_feedback_gains_batch, validation included.  V_bar [B][NV].
+ *   hessian      enum mmpc_hessian.  AUTO means EXACT wherever the model has second derivatives, as for the gains;
+ *                GAUSS_NEWTON is available and is NOT the true derivative.
+ *   x0_bar       [B][nx]          u_prev_bar  [B][nu]          traj_bar  [B][N][nx]
+ *   weights_bar  [B][nx+2nu], always per instance: a caller with shared weights sums the rows
+ *   adj_V        [B][NV], the direction a
+ *   vjp_status   [B]
+ *   Every output and vjp_status may be NULL.
+ *   workspace    DEVICE memory of mmpc_solve_vjp_workspace_bytes(h, B) bytes for the per-stage records G_k | kff_k
+ *                (nu (K + 1) doubles per stage; ceil(B / 64) blocks of N nu (K + 1) x 64 doubles, lane-interleaved).  The
+ *                kernel evaluates [A_k | B_k] again in the forward sweep, it is not stored.
+ * Backward-only mode: when traj_bar, weights_bar and adj_V are all NULL no record is stored, no forward sweep runs and
+ * workspace may be NULL; x0_bar and u_prev_bar are bit for bit those of the full call.  Otherwise a workspace that is
+ * NULL or smaller than the query: MMPC_ERR_INVALID_ARG naming `workspace` / `workspace_bytes`.
+ * Refused with MMPC_ERR_UNSUPPORTED: a linear-mode model; a handle with any finite state bound.  n_pin outside 0..N-1,
+ * a bad bounds_stride or weights_stride, an unknown hessian, a NULL V_bar: MMPC_ERR_INVALID_ARG, mmpc_last_error names
+ * the argument.  Everything is checked from the arguments alone before any device call; B = 0 is a no-op success.
+ * mmpc_solve_vjp_batch takes DEVICE pointers and is one stream-ordered launch on `stream` that never synchronises and
+ * never allocates (the handle's workspace is not used; mmpc_reserve_workspace's sizes are unchanged), so it can be
+ * captured in a hipGraph.  mmpc_solve_vjp_batch_host takes host pointers, stages them, brings its own workspace and is
+ * synchronous.  Multi-device and RCCL entries, state-bounded handles, a 16-lane kernel: out of scope. */
+int mmpc_solve_vjp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes);
+int mmpc_solve_vjp_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                         const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                         int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian, double* x0_bar,
+                         double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V, int32_t* vjp_status,
+                         void* workspace, uint64_t workspace_bytes, void* stream);
+int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian,
+                              double* x0_bar, double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V,
+                              int32_t* vjp_status);
+
 /* Continuous-time linearisation at (x[b], u[b]): A = df/dx [nx*nx], B = df/du [nx*nu]
  * column-major, xdot = f(x,u) [nx].  DEVICE pointers; any output may be NULL. */
 int mmpc_linearize_batch(mmpc_handle* h, int64_t B, const double* x, const double* u,

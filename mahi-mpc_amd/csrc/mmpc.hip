@@ -24,6 +24,7 @@
 
 #include "../../include/mmpc.h"
 #include "json_lite.h"
+#include "adjoint_sweep.h"
 #include "gain_sweep.h"
 #include "group_launch.h"
 #include "lane_launch.h"
@@ -1422,6 +1423,116 @@ int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact) {
     });
 }
 
+// ---- reverse-mode product of the solve (mmpc_solve_vjp_batch; adjoint_sweep.h) ----
+struct VjpArgs {
+    int64_t B = 0;
+    const double *V = nullptr, *u_prev = nullptr, *traj = nullptr, *weights = nullptr;
+    int64_t weights_stride = 0;
+    const double *u_lb = nullptr, *u_ub = nullptr;
+    int64_t bounds_stride = 0;
+    int32_t n_pin = 0;
+    const double* V_bar = nullptr;
+    int32_t hessian = 0;
+    double *x0_bar = nullptr, *u_prev_bar = nullptr, *traj_bar = nullptr, *weights_bar = nullptr, *adj_V = nullptr;
+    int32_t* status = nullptr;
+    void* workspace = nullptr;
+    uint64_t workspace_bytes = 0;
+    hipStream_t stream = nullptr;
+    bool forward() const { return traj_bar || weights_bar || adj_V; }   // else backward-only: no record, no workspace
+};
+// bytes of the record workspace of B instances: ceil(B / 64) blocks of (doubles per lane) x 64, lane-interleaved
+uint64_t vjp_workspace_bytes(const mmpc_model_info& mi, int64_t B) {
+    const uint64_t blocks = (static_cast<uint64_t>(B) + 63) / 64;
+    return blocks * static_cast<uint64_t>(adjoint_lane_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes)) * 64 *
+           sizeof(double);
+}
+// The one check of a VJP call's arguments: pure arithmetic on the arguments and the handle, before any device call
+// (check_gain_args's rules; the host entry brings its own workspace and passes check_workspace = false).
+int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool* exact) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    const mmpc_model_info& mi = h->info;
+    const int N = mi.num_shooting_nodes;
+    if (a.n_pin < 0 || a.n_pin > N - 1)
+        return fail(MMPC_ERR_INVALID_ARG, "n_pin must be 0 .. N - 1 (" + std::to_string(N - 1) + "), got " +
+                                              std::to_string(a.n_pin));
+    if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(mi, a.bounds_stride)) return rc;
+    if (a.hessian < MMPC_HESSIAN_AUTO || a.hessian > MMPC_HESSIAN_EXACT)
+        return fail(MMPC_ERR_INVALID_ARG, "hessian: not an mmpc_hessian value (" + std::to_string(a.hessian) + ")");
+    if (mi.is_linear) return fail(MMPC_ERR_UNSUPPORTED, "the solve VJP is not available for a linear-mode model");
+    {
+        std::lock_guard<std::mutex> lk(h->xb_mu);
+        if (h->x_bounded)
+            return fail(MMPC_ERR_UNSUPPORTED, "the solve VJP is not available with finite state bounds "
+                                              "(barrier-smoothed sensitivities are not computed)");
+    }
+    bool has_hess = false;
+    with_model(mi.model_id, [&](auto* m) {
+        has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
+        return MMPC_OK;
+    });
+    if (a.hessian == MMPC_HESSIAN_EXACT && !has_hess)
+        return fail(MMPC_ERR_UNSUPPORTED, "hessian = EXACT: the model has no second derivatives");
+    *exact = a.hessian != MMPC_HESSIAN_GAUSS_NEWTON && has_hess;
+    if (a.B == 0) return MMPC_OK;
+    if (!a.V || !a.u_prev || !a.traj || !a.weights) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
+    if (!a.V_bar) return fail(MMPC_ERR_INVALID_ARG, "V_bar is NULL");
+    if (a.weights_stride != 0 && a.weights_stride < mi.num_x + 2 * mi.num_u)
+        return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
+    if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
+    if (check_workspace && a.forward()) {
+        const uint64_t need = vjp_workspace_bytes(mi, a.B);
+        if (!a.workspace)
+            return fail(MMPC_ERR_INVALID_ARG, "workspace is NULL: traj_bar, weights_bar and adj_V need " +
+                                                  std::to_string(need) + " bytes (mmpc_solve_vjp_workspace_bytes)");
+        if (a.workspace_bytes < need)
+            return fail(MMPC_ERR_INVALID_ARG, "workspace_bytes is " + std::to_string(a.workspace_bytes) + ", needs " +
+                                                  std::to_string(need) + " (mmpc_solve_vjp_workspace_bytes)");
+    }
+    return MMPC_OK;
+}
+// a VJP call whose arguments check_vjp_args has passed, B > 0, device pointers, on the current device: one launch,
+// stream-ordered, no allocation, no synchronisation
+int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact) {
+    const mmpc_model_info& mi = h->info;
+    AdjointParams p{};
+    p.B = a.B;
+    p.N = mi.num_shooting_nodes;
+    p.h = mi.step_size;
+    p.V = a.V;
+    p.u_prev = a.u_prev;
+    p.traj = a.traj;
+    p.weights = a.weights;
+    p.w_stride = a.weights_stride;
+    p.u_lb = a.u_lb;
+    p.u_ub = a.u_ub;
+    p.b_stride = static_cast<int32_t>(a.bounds_stride);
+    p.n_pin = a.n_pin;
+    p.V_bar = a.V_bar;
+    p.x0_bar = a.x0_bar;
+    p.u_prev_bar = a.u_prev_bar;
+    p.traj_bar = a.traj_bar;
+    p.weights_bar = a.weights_bar;
+    p.adj_V = a.adj_V;
+    p.status = a.status;
+    p.ws = a.forward() ? static_cast<double*>(a.workspace) : nullptr;
+    const bool bounded = a.u_lb || a.u_ub;
+    const auto launch = [&](auto* k) -> int {
+        k<<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
+        MMPC_HIP(hipGetLastError());
+        return MMPC_OK;
+    };
+    return with_model(mi.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        if constexpr (HasHess<M>::value) {
+            if (exact)
+                return bounded ? launch(&adjoint_lane_kernel<M, true, true>)
+                               : launch(&adjoint_lane_kernel<M, true, false>);
+        }
+        return bounded ? launch(&adjoint_lane_kernel<M, false, true>) : launch(&adjoint_lane_kernel<M, false, false>);
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -1787,6 +1898,100 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
     if ((rc = launch_gains(h, a, exact))) return rc;
     MMPC_HIP(hipMemcpyAsync(G_out, d + off_G, nG * sizeof(double), hipMemcpyDeviceToHost, s));
     if (gain_status) MMPC_HIP(hipMemcpyAsync(gain_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MMPC_HIP(hipStreamSynchronize(s));
+    return MMPC_OK;
+}
+
+int mmpc_solve_vjp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes) {
+    if (!h || !bytes || B < 0) return fail(MMPC_ERR_INVALID_ARG, "null argument or B < 0");
+    *bytes = vjp_workspace_bytes(h->info, B);
+    return MMPC_OK;
+}
+
+int mmpc_solve_vjp_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                         const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                         int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian, double* x0_bar,
+                         double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V, int32_t* vjp_status,
+                         void* workspace, uint64_t workspace_bytes, void* stream) {
+    const VjpArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, V_bar, hessian,
+                    x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status, workspace, workspace_bytes,
+                    reinterpret_cast<hipStream_t>(stream)};
+    bool exact = false;
+    if (int rc = check_vjp_args(h, a, true, &exact)) return rc;
+    if (B == 0) return MMPC_OK;
+    int dev;
+    int rc = resolve_device(h, &dev);
+    if (rc) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    return launch_vjp(h, a, exact);
+}
+
+int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian,
+                              double* x0_bar, double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V,
+                              int32_t* vjp_status) {
+    VjpArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, V_bar, hessian,
+              x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status};
+    bool exact = false;
+    if (int rc = check_vjp_args(h, a, false, &exact)) return rc;   // before the strides size a copy
+    if (B == 0) return MMPC_OK;
+    std::lock_guard<std::mutex> lk(h->host_mu);
+    const mmpc_model_info& mi = h->info;
+    const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v, nw = nx + 2 * nu;
+    const size_t nW = weights_stride ? static_cast<size_t>(B) * static_cast<size_t>(weights_stride) : nw;
+    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
+    const size_t nB = (bounds_stride ? static_cast<size_t>(B) - 1 : 0) * static_cast<size_t>(bounds_stride) + nu;
+    const size_t nWs = a.forward() ? vjp_workspace_bytes(mi, B) / sizeof(double) : 0;
+    const size_t off_V = 0, off_Vb = off_V + B * NV, off_up = off_Vb + B * NV, off_tr = off_up + B * nu;
+    const size_t off_w = off_tr + B * N * nx, off_lb = off_w + nW, off_ub = off_lb + nB, off_x0b = off_ub + nB;
+    const size_t off_upb = off_x0b + B * nx, off_trb = off_upb + B * nu, off_wb = off_trb + B * N * nx;
+    const size_t off_a = off_wb + B * nw, off_ws = off_a + B * NV, off_st = off_ws + nWs;
+    const size_t total = off_st + (B + 1) / 2;
+    int dev;
+    int rc = resolve_device(h, &dev);
+    if (rc) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    rc = ensure_host_ctx(h, total * sizeof(double));
+    if (rc) return rc;
+    double* d = h->d_buf;
+    hipStream_t s = h->host_stream;
+    MMPC_HIP(hipMemcpyAsync(d + off_V, V, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_Vb, V_bar, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_up, u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_tr, traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(d + off_w, weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
+    a.V = d + off_V;
+    a.V_bar = d + off_Vb;
+    a.u_prev = d + off_up;
+    a.traj = d + off_tr;
+    a.weights = d + off_w;
+    a.u_lb = u_lb ? d + off_lb : nullptr;
+    a.u_ub = u_ub ? d + off_ub : nullptr;
+    a.x0_bar = x0_bar ? d + off_x0b : nullptr;
+    a.u_prev_bar = u_prev_bar ? d + off_upb : nullptr;
+    a.traj_bar = traj_bar ? d + off_trb : nullptr;
+    a.weights_bar = weights_bar ? d + off_wb : nullptr;
+    a.adj_V = adj_V ? d + off_a : nullptr;
+    a.status = dst;
+    a.workspace = nWs ? d + off_ws : nullptr;
+    a.workspace_bytes = nWs * sizeof(double);
+    a.stream = s;
+    if ((rc = launch_vjp(h, a, exact))) return rc;
+    const auto back = [&](double* dst_host, size_t off, size_t n) {
+        return dst_host ? hipMemcpyAsync(dst_host, d + off, n * sizeof(double), hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    MMPC_HIP(back(x0_bar, off_x0b, B * nx));
+    MMPC_HIP(back(u_prev_bar, off_upb, B * nu));
+    MMPC_HIP(back(traj_bar, off_trb, B * N * nx));
+    MMPC_HIP(back(weights_bar, off_wb, B * nw));
+    MMPC_HIP(back(adj_V, off_a, B * NV));
+    if (vjp_status) MMPC_HIP(hipMemcpyAsync(vjp_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MMPC_HIP(hipStreamSynchronize(s));
     return MMPC_OK;
 }

@@ -48,6 +48,8 @@ BARRIER_MONOTONE, BARRIER_MEHROTRA = 0, 1
 # kernel of the feedback-gain sweep (enum mmpc_gain_kernel) and its per-instance status
 GAIN_KERNEL_AUTO, GAIN_KERNEL_LANE, GAIN_KERNEL_GROUP = 0, 1, 2
 GAIN_OK, GAIN_GAUSS_NEWTON_FALLBACK, GAIN_FAILED = 0, 1, 2
+# per-instance status of the solve VJP (mmpc_solve_vjp_batch): the same three values
+VJP_OK, VJP_GAUSS_NEWTON_FALLBACK, VJP_FAILED = 0, 1, 2
 MODEL_TWO_LINK_ARM, MODEL_EXO_ARM, MODEL_USER = 0, 1, 2
 USER_LIB_DIR = os.path.join(ROOT, "lib", "user")
 BUILTIN_MODELS = ("two_link_arm", "double_pendulum", "exo_arm", "exo")  # "mmpc_model" names libmmpc.so serves   # models generated from SX by ModelGenerator (make -C host user)
@@ -129,6 +131,12 @@ def lib(path: str | None = None):
         _gain = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64] + [C.c_int32] * 4)
         L.mmpc_feedback_gains_batch.argtypes = _gain + [_vp] * 3
         L.mmpc_feedback_gains_batch_host.argtypes = _gain + [_vp] * 2
+        # solve VJP: (V, u_prev, traj, weights), weights_stride, (u_lb, u_ub), bounds_stride, n_pin, V_bar, hessian,
+        # (x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status[, workspace, workspace_bytes, stream])
+        _vjp = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int32] + [_vp] * 6)
+        L.mmpc_solve_vjp_batch.argtypes = _vjp + [_vp, C.c_uint64, _vp]
+        L.mmpc_solve_vjp_batch_host.argtypes = _vjp
+        L.mmpc_solve_vjp_workspace_bytes.argtypes = [_vp, C.c_int64, C.POINTER(C.c_uint64)]
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -477,6 +485,72 @@ class Solver:
                                                            _ptr(weights), ws, _ptr(lb), _ptr(ub), bs, int(n_pin),
                                                            n_gain, int(hessian), int(kernel), _ptr(G), _ptr(st)))
         return G, st
+
+    def solve_vjp_workspace_bytes(self, B) -> int:
+        """Bytes of the record workspace a full solve_vjp of B instances needs (mmpc_solve_vjp_workspace_bytes)."""
+        n = C.c_uint64(0)
+        self._check(self._L.mmpc_solve_vjp_workspace_bytes(self._h, B, C.byref(n)))
+        return int(n.value)
+
+    def solve_vjp(self, B, V, u_prev, traj, weights, V_bar, x0_bar=None, u_prev_bar=None, traj_bar=None,
+                  weights_bar=None, adj_V=None, vjp_status=None, workspace=None, workspace_bytes=None,
+                  weights_stride=0, u_lb=None, u_ub=None, bounds_stride=0, n_pin=0, hessian=HESSIAN_AUTO,
+                  backward_only=False, stream=None):
+        """Reverse-mode product of the solve at V (mmpc_solve_vjp_batch; device tensors, one stream-ordered launch):
+        theta_bar = (d V* / d theta)^T V_bar for theta = x0, u_prev, traj and the weights.  Returns a dict with x0_bar
+        [B, nx], u_prev_bar [B, nu], traj_bar [B, N, nx], weights_bar [B, nx + 2 nu] (per instance: sum the rows for
+        shared weights), adj_V [B, NV] and vjp_status [B] int32 (0 as asked, 1 Gauss-Newton fallback, 2 failed: rows
+        0).  Outputs and the workspace are torch tensors on V's device unless given (tensors or raw addresses, used as
+        given; a raw workspace address needs workspace_bytes).  backward_only: only x0_bar, u_prev_bar and vjp_status
+        -- no forward sweep, no workspace; traj_bar, weights_bar and adj_V are then None."""
+        nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
+        out = dict(x0_bar=x0_bar, u_prev_bar=u_prev_bar, traj_bar=traj_bar, weights_bar=weights_bar, adj_V=adj_V,
+                   vjp_status=vjp_status)
+        shapes = dict(x0_bar=(B, nx), u_prev_bar=(B, nu), traj_bar=(B, N, nx), weights_bar=(B, nx + 2 * nu),
+                      adj_V=(B, NV), vjp_status=(B,))
+        fwd = ("traj_bar", "weights_bar", "adj_V")
+        if backward_only and any(out[k] is not None for k in fwd):
+            raise ValueError("backward_only takes no traj_bar, weights_bar or adj_V")
+        want = [k for k in out if out[k] is None and not (backward_only and k in fwd)]
+        if want or (workspace is None and not backward_only):
+            import torch
+            for k in want:
+                out[k] = torch.empty(shapes[k], dtype=torch.int32 if k == "vjp_status" else torch.float64,
+                                     device=V.device)
+            if workspace is None and not backward_only:
+                workspace = torch.empty((max(self.solve_vjp_workspace_bytes(B), 8) // 8,), dtype=torch.float64,
+                                        device=V.device)
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else 0
+        self._check(self._L.mmpc_solve_vjp_batch(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                 weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                 int(n_pin), _ptr(V_bar), int(hessian), _ptr(out["x0_bar"]),
+                                                 _ptr(out["u_prev_bar"]), _ptr(out["traj_bar"]),
+                                                 _ptr(out["weights_bar"]), _ptr(out["adj_V"]),
+                                                 _ptr(out["vjp_status"]), _ptr(workspace), int(workspace_bytes),
+                                                 stream))
+        return out
+
+    def solve_vjp_host(self, V, u_prev, traj, weights, V_bar, u_lb=None, u_ub=None, n_pin=0, hessian=HESSIAN_AUTO,
+                       backward_only=False):
+        """solve_vjp for numpy arrays, synchronous (mmpc_solve_vjp_batch_host; the library brings the workspace);
+        u_lb / u_ub [nu] shared or [B, nu] per instance.  Returns a dict of numpy arrays with solve_vjp's keys."""
+        nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
+        V = _f64(V, (-1, NV))
+        B = V.shape[0]
+        u_prev, traj, weights, V_bar = _f64(u_prev, (B, nu)), _f64(traj, (B, N, nx)), _f64(weights), _f64(V_bar, (B, NV))
+        ws = 0 if weights.ndim == 1 else weights.shape[-1]
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)
+        out = dict(x0_bar=np.zeros((B, nx)), u_prev_bar=np.zeros((B, nu)),
+                   traj_bar=None if backward_only else np.zeros((B, N, nx)),
+                   weights_bar=None if backward_only else np.zeros((B, nx + 2 * nu)),
+                   adj_V=None if backward_only else np.zeros((B, NV)), vjp_status=np.full(B, -1, np.int32))
+        self._check(self._L.mmpc_solve_vjp_batch_host(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights), ws,
+                                                      _ptr(lb), _ptr(ub), bs, int(n_pin), _ptr(V_bar), int(hessian),
+                                                      _ptr(out["x0_bar"]), _ptr(out["u_prev_bar"]),
+                                                      _ptr(out["traj_bar"]), _ptr(out["weights_bar"]),
+                                                      _ptr(out["adj_V"]), _ptr(out["vjp_status"])))
+        return out
 
     def set_state_bounds(self, x_lb=None, x_ub=None):
         """x_lb <= x_k <= x_ub for k = 1..N (None = unbounded); finite bounds select the interior-point variant."""
