@@ -734,8 +734,12 @@ int lane_ws_doubles(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
 }
 // LDS of one instance group of the 16-lane kernel, and of a full workgroup of kGroupsPerWave of them
 size_t group_lds_instance_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
+    // the constant block of the model's kernels (sqp_group.h GroupLaneOps; generated models: none)
+    const int kc = mi.model_id == MMPC_MODEL_TWO_LINK_ARM ? mmpc::GroupLaneOps<TwoLinkArm>::doubles
+                   : mi.model_id == MMPC_MODEL_EXO_ARM    ? mmpc::GroupLaneOps<ExoArm>::doubles
+                                                          : 0;
     return static_cast<size_t>(mmpc::group_lds_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.ub,
-                                                       mi.is_linear != 0, v.xb)) * sizeof(double);
+                                                       mi.is_linear != 0, v.xb, kc)) * sizeof(double);
 }
 size_t group_lds_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
     return group_lds_instance_bytes(mi, nq, v) * kGroupsPerWave;

@@ -48,23 +48,44 @@ __host__ __device__ constexpr bool w_struct_zero<TwoLinkArm>(int r, int j) { ret
 // Packed record of the x rows of W_k for the on-chip W path of the unbounded exact-Hessian kernel (sqp_group_kernel,
 // WLDS): PK doubles per stage, idx(r, j) = slot of W_k[r][j] (x row r, column j of (x, u)), -1 for a structural zero.
 // PK = 0: the model has no packing and keeps the workspace path.  2-link arm: eval_hess writes W[i][j] and W[j][i]
-// from one variable, so the 14 non-zero entries of the x rows are 10 distinct values:
+// from one variable, so the 14 non-zero entries of the x rows are 10 distinct values.  The slot of W[r][j] is
+// col(r) + col(j) with col = (0, 1, 2, 4, 6, 8): distinct over the 10 values, and a lane's row is then ONE address,
+// record + col(r), plus the immediate offsets col(j) -- one address register for the sweep's six loads:
 //   slot  0     1     2     3     4     5     6     7     8     9
-//   W     [0][0] [0][1] [1][1] [1][2] [1][3] [1][4] [1][5] [2][2] [2][3] [3][3]
+//   W     [0][0] [0][1] [1][1] [1][2] [2][2] [1][3] [2][3] [1][4] [3][3] [1][5]
+// A structural zero W[r][j] has no slot; read at col(r) + col(j) all the same (under a factor 0, sqp_group_kernel) it
+// lands on another entry's slot or up to OVER = col(NX - 1) + col(NX + NU - 1) - (PK - 1) doubles past the record.
 template <class Model>
 struct WPack {
-    static constexpr int PK = 0;
+    static constexpr int PK = 0, OVER = 0;
+    __host__ __device__ static constexpr int col(int) { return 0; }
     __host__ __device__ static constexpr int idx(int, int) { return -1; }
 };
 template <>
 struct WPack<TwoLinkArm> {
-    static constexpr int PK = 10;
+    static constexpr int PK = 10, OVER = 3;
+    __host__ __device__ static constexpr int col(int i) { return i < 3 ? i : 2 * (i - 1); }
     __host__ __device__ static constexpr int idx(int r, int j) {
         if (w_struct_zero<TwoLinkArm>(r, j)) return -1;
-        const int a = r < j ? r : j, b = r < j ? j : r;   // (a, b), a <= b: the entry eval_hess computes
-        return a == 0 ? b : (a == 1 ? 1 + b : (a == 2 ? 5 + b : 9));
+        return col(r) + col(j);
     }
 };
+// the additive slots are a packing: inside the record, and shared only by W[r][j] and W[j][r]
+template <class Model>
+__host__ __device__ constexpr bool wpack_valid() {
+    using P = WPack<Model>;
+    constexpr int NX = Model::NX, KZ = Model::NX + Model::NU;
+    for (int r = 0; r < NX; ++r)
+        for (int j = 0; j < KZ; ++j) {
+            if (P::idx(r, j) < 0) continue;
+            if (P::idx(r, j) >= P::PK || P::idx(r, j) != P::col(r) + P::col(j)) return false;
+            for (int r2 = 0; r2 < NX; ++r2)
+                for (int j2 = 0; j2 < KZ; ++j2)
+                    if (P::idx(r2, j2) == P::idx(r, j) && !((r2 == r && j2 == j) || (r2 == j && j2 == r))) return false;
+        }
+    return P::OVER == P::col(NX - 1) + P::col(KZ - 1) - (P::PK - 1);
+}
+static_assert(wpack_valid<TwoLinkArm>(), "W record of the 2-link arm");
 // first column whose structural zeros sit in the same x rows as column j's (j itself when there is none before it)
 template <class Model>
 __host__ __device__ constexpr int wpack_col_rep(int j) {
@@ -79,7 +100,7 @@ constexpr int kGroupLanes = 16;
 constexpr int kGroupsPerWave = 4;
 
 // LDS doubles per instance.  The hold targets (bounded solves) and the linear-mode block are only allocated
-// when used: at cfg#2 that keeps a 4-instance workgroup at 39.0 KB (bounded: 39.75 KB), so 4 workgroups (one per
+// when used: at cfg#2 that keeps a 4-instance workgroup at 39,040 B (bounded: 40,960 B), so 4 workgroups (one per
 // SIMD) fit a CU's 160 KB.  nq = kinematic rows of the model (sqp_lane.h a_mul); the stage blocks are h da/dq,
 // h da/dz, h da/du.  xb (the interior-point variant) adds nothing here since round 5: its per-stage z_l, z_u, Sigma,
 // b, z_u - z_l live in the HBM workspace (group_ws_doubles) -- in LDS they made 67.8 KB per workgroup at cfg#2, two
@@ -89,13 +110,35 @@ constexpr int kGroupsPerWave = 4;
 // shorter than sFqd's overreach of 2 (nx - nq)^2 doubles (exo shapes at N = 1), a tail pad of that size keeps the read
 // inside the instance's own block, never in the next group's block or past the end of the dynamic LDS; otherwise no
 // pad (round 4 always padded: the control-bounded cfg#2 layout was then 40,960 B per workgroup).  The prefetched
-// values are never used.
+// values are never used.  (A lane that reads the constant block below does so with stage stride 0 and overreaches
+// nothing; the block sits last, after the pad, so the overreach of the other lanes still lands in front of it.)
+// kc: doubles of the constant block that closes the instance's LDS in the kernels of a model with per-lane sweep
+// operands (GroupLaneOps, below), [nx - 1 zeros | h | max(nx, nu) zeros].  Their serial sweeps read "this lane's row or
+// column of A_k" through a per-lane address and a per-lane stage stride: a lane with the role points into the stage
+// blocks, a q-lane's row h e_{nq+r} and the zero row of a lane without the role point here with stride 0 (cfg#2: 8
+// doubles, 39,040 B per workgroup).
+__host__ __device__ constexpr int group_const_doubles(int nx, int nu) {
+    return nx + nu < kGroupLanes ? nx + (nx > nu ? nx : nu) : 0;
+}
 __host__ __device__ constexpr int group_lds_doubles(int nx, int nu, int nq, int N, bool bounded = true,
-                                                   bool linear = true, bool xb = false) {
+                                                   bool linear = true, bool xb = false, int kc = 0) {
     return N * (3 * nx + (nx - nq) * (nq + (nx - nq) + nu) + 2 * nu) + 3 * (N + 1) * nx + (bounded ? N * nu : 0) +
            (linear ? (nx - nq) * (nq + (nx - nq) + nu) + nx : 0) +
-           (N * ((nx - nq) * nu + nx) >= 2 * (nx - nq) * (nx - nq) ? 0 : 2 * (nx - nq) * (nx - nq));
+           (N * ((nx - nq) * nu + nx) >= 2 * (nx - nq) * (nx - nq) ? 0 : 2 * (nx - nq) * (nx - nq)) + kc;
 }
+// Models whose 16-lane kernels take the sweeps' lane operands through per-lane addresses, at the price of the constant
+// block: the 2-link arm (cfg#2, whose kernel is bound by the issue slots of one wave).  The other models keep the
+// FP64 blends against the lane-role factors and their LDS layout to the byte: the exo's block would be 16 doubles per
+// instance, and LDS is what sizes its launches -- three of its groups share a 64 KB resume workgroup at N = 26 with 21
+// bytes to spare (mmpc.hip tail_plan), and its kernels spill registers, so they are not bound by issue slots.
+template <class Model>
+struct GroupLaneOps {
+    static constexpr int doubles = 0;
+};
+template <>
+struct GroupLaneOps<TwoLinkArm> {
+    static constexpr int doubles = group_const_doubles(TwoLinkArm::NX, TwoLinkArm::NU);
+};
 // exact Hessian (EXACT): per stage the x rows of W_k = h sum_s lam_{k+1,NQ+s} d^2 acc_s/d(x,u)^2 (nx x (nx+nu))
 // and its u-u block (nu x nu), written stage-parallel and read by the lane-distributed Riccati sweep
 __host__ __device__ constexpr int group_hess_doubles(int nx, int nu) { return nx * (nx + nu) + nu * nu; }
@@ -120,7 +163,8 @@ __host__ __device__ constexpr int group_ws_doubles(int nx, int nu, int N, bool b
 // the cfg#2 shape (2-link arm, N = 30, unbounded): four instances per workgroup within 40,960 B of LDS, so that four
 // workgroups (one per SIMD) fit a CU -- the on-chip W record lives in arrays that are dead while it is alive and adds
 // nothing to this
-static_assert(kGroupsPerWave * group_lds_doubles(4, 2, 2, 30, false, false, false) * 8 <= 40960, "cfg#2 LDS budget");
+static_assert(kGroupsPerWave * group_lds_doubles(4, 2, 2, 30, false, false, false, GroupLaneOps<TwoLinkArm>::doubles) * 8 <= 40960,
+              "cfg#2 LDS budget");
 
 struct GroupWork {
     double* ws;
@@ -255,7 +299,9 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     const double h = p.h;
 
     // ---- LDS views of this instance ----
-    double* const sX = shm + gi * group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB);  // [N+1][NX]
+    // constant block of the per-lane sweep operands (LOPS, below): the models with GroupLaneOps, lane-distributed path
+    constexpr int KC = NX + NU < kGroupLanes ? GroupLaneOps<Model>::doubles : 0;
+    double* const sX = shm + gi * group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC);  // [N+1][NX]
     // sD | sDX | sDU are contiguous: between the W pass and the step sweep of an iteration all three are dead (d / lam
     // in sD: the W pass is its last reader; sDX, sDU: the previous step, consumed by the update) and, on the on-chip W
     // path (WLDS), sD + NX .. holds the packed W records (sW) -- d_0 = 0 in sD[0..NX) stays
@@ -282,6 +328,14 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     constexpr int KZ = NX + NU, HW = group_hess_doubles(NX, NU);
     double* const wH = wK + N * NU * (NS + 1);  // EXACT: [N][HW] = W_k x rows [NX][KZ] | W_k uu block [NU][NU]
     double* const sW = sD + NX;                 // WLDS: [N][PK] packed W_k x rows, over sD[1..], sDX and sDU
+    // WLDS: the sweep's loads of the last record's structural zeros reach the OVER doubles behind it (WPack).  Those
+    // lie inside sDX | sDU (OVER <= NX and PK <= 2 NX + NU): zeroed here for the first iteration, and from then on a
+    // step of the previous iteration, finite whenever the iteration goes on to its Riccati sweep -- the line search
+    // accepts a non-finite step only into an iterate that the next stop test leaves with ST_NONFINITE.
+    static_assert(!WLDS || WPack<Model>::OVER <= NX, "the over-read of the last W record stays inside sDU");
+    if constexpr (WLDS) {
+        if (gl < WPack<Model>::OVER) sW[N * PK + gl] = 0.0;
+    }
     constexpr int NR = NS + NU + 1;             // BOUNDED: [N][NU][NR] = un-held [H_wx | -R | H_ww | h_w] rows
     double* const wRel = wH + N * HW;
     bool w_zeros_stored = false;   // W_k's structural zeros are in the workspace (this launch's first W pass stored them)
@@ -333,27 +387,29 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     const int ru = lu ? r - NX : 0;                   // u row
     const int ta = la ? r - NQ : 0;                   // row of the a-blocks (hFq, hFqd, hFu) of an a-lane
     const double Qr = lx ? w[rx] : 0.0;               // Q of this lane's x row
-    // lane-role masks as blend factors: the DIST loops blend loaded values with FMAs instead of selects (a select
-    // of an LDS load becomes a branch or a pointer select)
-    const double lqd = r < NQ ? 1.0 : 0.0, lad = la ? 1.0 : 0.0;
+    // lane-role masks as blend factors, for the models whose row / column of A is not a per-lane load (LOPS, ACOLP,
+    // below): their DIST loops blend loaded values with FMAs instead of selects (a select of an LDS load becomes a
+    // branch or a pointer select)
+    [[maybe_unused]] const double lqd = r < NQ ? 1.0 : 0.0, lad = la ? 1.0 : 0.0;
     // x-lane factor for the sweeps' per-stage masking: one FP64 multiply where a 64-bit select is two cndmasks (the
     // masked values are finite sums of this instance's own data, so 0 * v == 0)
     const double lxf = lx ? 1.0 : 0.0;
-    // WLDS: slot of W_k[r][j] in the packed record and its blend factor.  A structural zero, and every column of a
-    // lane without an x row, reads slot 0 (finite) under a factor 0 -- the factor takes the place of the x-lane factor
-    // at the uses of W, so the sweep gains no select; columns with the same zero pattern share one factor.
-    int wofs[KZ];
+    // WLDS: W_k[r][j] sits at slot wrow + col(j) of the packed record, wrow = col(r) this lane's one row offset (a lane
+    // without an x row: row 0), and wm[j] is its blend factor.  A structural zero, and every column of a lane without
+    // an x row, reads its additive slot all the same -- another entry of this record, or up to OVER doubles past it, all
+    // finite (sW, below) -- under a factor 0; the factor takes the place of the x-lane factor at the uses of W, so the
+    // sweep gains no select; columns with the same zero pattern share one factor.
+    int wrow = 0;
+#pragma unroll
+    for (int r2 = 0; r2 < NX; ++r2)
+        if (lx && r == r2) wrow = WPack<Model>::col(r2);
     double wm[KZ];
 #pragma unroll
     for (int j = 0; j < KZ; ++j) {
-        wofs[j] = 0;
         bool nz = false;
 #pragma unroll
         for (int r2 = 0; r2 < NX; ++r2)
-            if (lx && r == r2 && WPack<Model>::idx(r2, j) >= 0) {
-                wofs[j] = WPack<Model>::idx(r2, j);
-                nz = true;
-            }
+            if (lx && r == r2 && WPack<Model>::idx(r2, j) >= 0) nz = true;
         wm[j] = wpack_col_rep<Model>(j) < j ? wm[wpack_col_rep<Model>(j)] : (nz ? 1.0 : 0.0);
     }
     const int rq = r < NQ ? r : 0;                    // q column of a q-lane (clamped)
@@ -373,11 +429,43 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     for (int z = 0; z < NQ; ++z) hq[z] = (r == NQ + z) ? h : 0.0;   // column r of A holds h in row z (kinematics)
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
-        hrow[j] = (r < NQ && j == NQ + r) ? h : 0.0;  // row r of A of a q-lane (besides the identity)
+        hrow[j] = (r < NQ && j == NQ + r) ? h : 0.0;  // row r of A of a q-lane (besides the identity); blended where !LOPS
         qoh[j] = (j == r) ? Qr : 0.0;
     }
 #pragma unroll
     for (int c = 0; c < NU; ++c) rdg[c] = (r == NX + c) ? R[c] : 0.0;
+    // LOPS (models with GroupLaneOps): this lane's row and column of A_k as LDS operands of the serial sweeps -- an address and a stage stride
+    // (bytes) per operand, both fixed for the launch.  A lane with the role reads the stage blocks (stride = block size);
+    // a q-lane's row h e_{NQ+r} and the zero row / column of a lane without the role are read from the constant block
+    // sKc = [NX - 1 zeros | h | max(NX, NU) zeros] with stride 0.  The loads are unconditional and deliver what the
+    // blends fma(lad, v, hrow) / lad v + lqd v' delivered (1 v + 0, or 0 v + h with v finite), without the FP64
+    // instructions -- the same idiom as the W slots (wrow): per-lane addresses, never a select of a loaded value.
+    constexpr bool LOPS = KC > 0;
+    double* const sKc = sX + group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC) - KC;
+    // (the addresses are LDS pointers, so that the base of the dynamic LDS is added here once and not at every load)
+    using LdsB = const __attribute__((address_space(3))) char*;
+    using LdsD = const __attribute__((address_space(3))) double*;
+    const LdsB shb = (LdsB)shm;
+    auto lds = [](LdsB b) { return *(LdsD)b; };
+    // a running address, opaque to the loop optimiser: one add per stage and immediate offsets from it (left alone,
+    // strength reduction gives every unrolled copy of a load its own induction variable)
+    auto pin = [](LdsB& b) { asm volatile("" : "+v"(b)); };
+    [[maybe_unused]] const LdsB iKc = shb + 8 * (int)(sKc - shm), iKz = iKc + 8 * NX;   // the block; its zero row (max(NX, NU) zeros)
+    // row r of [A - I | B]: a-lanes [hFq | hFqd | hFu] row r - NQ, q-lanes h e_{NQ+r} | 0, other lanes 0
+    [[maybe_unused]] const LdsB iAq = la ? shb + 8 * ((int)(sFq - shm) + ta * NQ) : (r < NQ ? iKc + 8 * ((NX - 1) - (NQ + r)) : iKz);
+    [[maybe_unused]] const int zAq = la ? 8 * FQ : 0, zAd = la ? 8 * FD : 0, zBr = la ? 8 * FU : 0;
+    [[maybe_unused]] const LdsB iAd = la ? shb + 8 * ((int)(sFqd - shm) + ta * NA) : (r < NQ ? iAq + 8 * NQ : iKz);
+    [[maybe_unused]] const LdsB iBr = la ? shb + 8 * ((int)(sFu - shm) + ta * NU) : iKz;
+    // column r of A's a-rows: a-lanes hFqd[:, r - NQ], q-lanes hFq[:, r], other lanes 0.  With NQ == NA both kinds of
+    // column have the element stride NA, an immediate; a lane without the role reads the block from its start, where
+    // the offsets t NA (t < NA) are zeros (they never meet h at NX - 1 = 2 NA - 1).  Other shapes keep the blend.
+    constexpr bool ACOLP = LOPS && NQ == NA && (NA - 1) * NA < KC;
+    [[maybe_unused]] const int zAc = (la || r < NQ) ? 8 * FD : 0;
+    [[maybe_unused]] const LdsB iAc = la ? shb + 8 * ((int)(sFqd - shm) + ta) : (r < NQ ? shb + 8 * ((int)(sFq - shm) + rq) : iKc),
+                                iAcN = iAc + (N - 1) * zAc;   // ... at the last stage
+    if constexpr (LOPS) {
+        for (int i = gl; i < KC; i += G) sKc[i] = (i == NX - 1) ? h : 0.0;
+    }
     // ---- load: V (reference layout) -> LDS, x_0 pinned (ModelControl.cpp:144-145) ----
     {
         const double* Vin = p.V + ii * (int64_t)NV;
@@ -936,16 +1024,18 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             return t;
         };
         // row r of [A - I | B] (x-lanes) at stage k: q-lanes h e_{NQ+r}, a-lanes [hFq, hFqd | hFu] row r - NQ
-        // (loads are unconditional from clamped rows and then selected: a conditional LDS load becomes a branch)
-        // (the asm pins keep the selects on values: select(load, hrow[j]) otherwise becomes a flat load through a
-        // selected LDS-or-scratch pointer)
+        // (unconditional loads through the lane's own index and stage stride, iAq / iAd / iBr above: a conditional LDS
+        // load becomes a branch, and a select between a loaded value and a register a flat load through a selected
+        // LDS-or-scratch pointer)
         auto load_arow = [&](int k, double* arow, double* brow) {
 #pragma unroll
-            for (int s2 = 0; s2 < NQ; ++s2) arow[s2] = fma(lad, sFq[k * FQ + ta * NQ + s2], hrow[s2]);
+            for (int s2 = 0; s2 < NQ; ++s2)
+                arow[s2] = LOPS ? lds(iAq + __mul24(k, zAq) + 8 * s2) : fma(lad, sFq[k * FQ + ta * NQ + s2], hrow[s2]);
 #pragma unroll
-            for (int s2 = 0; s2 < NA; ++s2) arow[NQ + s2] = fma(lad, sFqd[k * FD + ta * NA + s2], hrow[NQ + s2]);
+            for (int s2 = 0; s2 < NA; ++s2)
+                arow[NQ + s2] = LOPS ? lds(iAd + __mul24(k, zAd) + 8 * s2) : fma(lad, sFqd[k * FD + ta * NA + s2], hrow[NQ + s2]);
 #pragma unroll
-            for (int c = 0; c < NU; ++c) brow[c] = lad * sFu[k * FU + ta * NU + c];
+            for (int c = 0; c < NU; ++c) brow[c] = LOPS ? lds(iBr + __mul24(k, zBr) + 8 * c) : lad * sFu[k * FU + ta * NU + c];
         };
         // d_{k+1} = A_k d_k + c_k (d_0 = 0): lane r holds d_k[r]
         // The recursions below are latency-bound (a few FMAs per stage on the dependency chain): every stage's
@@ -953,24 +1043,32 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         auto d_recursion_dist = [&]() {
             double dr = 0.0;
             if (lx) sD[rx] = 0.0;
-            // stage operands as loaded (the blend with the lane-role factors happens at the use, so the wait for a
-            // load sits a full stage after its issue): two buffers, each refilled two stages ahead
+            // stage operands (row r of A - I through the lane's own address, used as loaded; the wait for a load sits a
+            // full stage after its issue): two buffers, each refilled two stages ahead
             struct Op {
                 double q[NQ > 0 ? NQ : 1], d[NA], c;
             };
+            // (the lane's two row addresses run along with the fetches, one add each per stage: fetch k is the k-th call)
+            LdsB jq = iAq, jd = iAd;
             auto fetch = [&](int k, Op& o) {
 #pragma unroll
-                for (int s2 = 0; s2 < NQ; ++s2) o.q[s2] = sFq[k * FQ + ta * NQ + s2];
+                for (int s2 = 0; s2 < NQ; ++s2) o.q[s2] = LOPS ? lds(jq + 8 * s2) : sFq[k * FQ + ta * NQ + s2];
 #pragma unroll
-                for (int s2 = 0; s2 < NA; ++s2) o.d[s2] = sFqd[k * FD + ta * NA + s2];
+                for (int s2 = 0; s2 < NA; ++s2) o.d[s2] = LOPS ? lds(jd + 8 * s2) : sFqd[k * FD + ta * NA + s2];
                 o.c = sC[k * NX + rx];
+                if constexpr (LOPS) {
+                    jq += zAq;
+                    jd += zAd;
+                    pin(jq);
+                    pin(jd);
+                }
             };
             auto stage = [&](int k, Op& o) {
                 double db[NX], arow[NX];
 #pragma unroll
-                for (int s2 = 0; s2 < NQ; ++s2) arow[s2] = fma(lad, o.q[s2], hrow[s2]);
+                for (int s2 = 0; s2 < NQ; ++s2) arow[s2] = LOPS ? o.q[s2] : fma(lad, o.q[s2], hrow[s2]);
 #pragma unroll
-                for (int s2 = 0; s2 < NA; ++s2) arow[NQ + s2] = fma(lad, o.d[s2], hrow[NQ + s2]);
+                for (int s2 = 0; s2 < NA; ++s2) arow[NQ + s2] = LOPS ? o.d[s2] : fma(lad, o.d[s2], hrow[NQ + s2]);
                 const double cr = o.c;
                 // unconditional and unclamped (static wait counts; the address is a strength-reduced increment): past
                 // the last stage the loads read the next arrays of this instance's LDS block (sFq -> sFqd -> sFu,
@@ -990,7 +1088,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             };
             Op o0, o1;
             fetch(0, o0);
-            fetch(N > 1 ? 1 : 0, o1);
+            fetch(LOPS || N > 1 ? 1 : 0, o1);   // LOPS: the second call, stage 1 (N = 1: stage N, as the prefetches below)
             int k = 0;
             for (; k + 1 < N; k += 2) {
                 stage(k, o0);
@@ -1000,12 +1098,21 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         };
         // adjoint + reduced gradient + Riccati backward sweep; lane r: row r of P~ (Prow) and p~ (pvr), lam[r]
         // column r of the a-rows of A at stage k: hFq[:, r] (q-lanes), hFqd[:, r - NQ] (a-lanes), 0 otherwise
-        auto load_acol = [&](int k, double* acol) {
+        // (ACOLP: jc = the lane's column address at stage k, kept by the caller, which takes the stages N - 1 .. 0 in order:
+        // it leaves here one stage down, one add per stage)
+        auto load_acol = [&](int k, [[maybe_unused]] LdsB& jc, double* acol) {
+            if constexpr (ACOLP) {
 #pragma unroll
-            for (int t2 = 0; t2 < NA; ++t2) {
-                double v = lad * sFqd[k * FD + t2 * NA + ta];
-                if constexpr (NQ > 0) v = fma(lqd, sFq[k * FQ + t2 * NQ + rq], v);
-                acol[t2] = v;
+                for (int t2 = 0; t2 < NA; ++t2) acol[t2] = lds(jc + 8 * t2 * NA);
+                jc -= zAc;
+                pin(jc);
+            } else {
+#pragma unroll
+                for (int t2 = 0; t2 < NA; ++t2) {
+                    double v = lad * sFqd[k * FD + t2 * NA + ta];
+                    if constexpr (NQ > 0) v = fma(lqd, sFq[k * FQ + t2 * NQ + rq], v);
+                    acol[t2] = v;
+                }
             }
         };
         // adjoint lam_k = Q e_{k-1} + A_k^T lam_{k+1} (lam_N = Q e_{N-1}, e_{k-1} = d_k + x_k - r_{k-1}), lane r holds
@@ -1028,11 +1135,23 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             struct Op {
                 double fd[NA], fq[NA], xk, trm, dk, zg;
             };
+            // ACOLP: the lane's column address runs down with the fetches, one add per stage and no clamp: fetch number
+            // i reads stage N - 1 - i, and the two fetches past stage 1 (values never used) read stages 0 and -1 of the
+            // lane's array -- the end of the array in front of it (sC, sFq), inside the instance's block
+            [[maybe_unused]] LdsB jc = iAcN;
             auto fetch = [&](int k, Op& o) {   // k >= 1
 #pragma unroll
                 for (int t2 = 0; t2 < NA; ++t2) {
-                    o.fd[t2] = sFqd[k * FD + t2 * NA + ta];
-                    if constexpr (NQ > 0) o.fq[t2] = sFq[k * FQ + t2 * NQ + rq];
+                    if constexpr (ACOLP) {
+                        o.fd[t2] = lds(jc + 8 * t2 * NA);
+                    } else {
+                        o.fd[t2] = sFqd[k * FD + t2 * NA + ta];
+                        if constexpr (NQ > 0) o.fq[t2] = sFq[k * FQ + t2 * NQ + rq];
+                    }
+                }
+                if constexpr (ACOLP) {
+                    jc -= zAc;
+                    pin(jc);
                 }
                 o.xk = sX[k * NX + rx];
                 o.trm = tr[(k - 1) * NX + rx];
@@ -1044,9 +1163,13 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 double acol[NA];
 #pragma unroll
                 for (int t2 = 0; t2 < NA; ++t2) {
-                    double v = lad * o.fd[t2];
-                    if constexpr (NQ > 0) v = fma(lqd, o.fq[t2], v);
-                    acol[t2] = v;
+                    if constexpr (ACOLP) {
+                        acol[t2] = o.fd[t2];
+                    } else {
+                        double v = lad * o.fd[t2];
+                        if constexpr (NQ > 0) v = fma(lqd, o.fq[t2], v);
+                        acol[t2] = v;
+                    }
                 }
                 double qe = Qr * (o.dk + (o.xk - o.trm));
                 if constexpr (XB) qe += o.zg;
@@ -1110,9 +1233,10 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             }
             double Prow[NS], pvr;
+            [[maybe_unused]] LdsB jcol = iAcN;   // load_acol's running address
             const double lxm = lx ? 1.0 : 0.0;
             // W_k row rx and uu block, loaded one stage ahead into one buffer: from the workspace, or (WLDS) row rx of
-            // the packed record in LDS through this lane's slots wofs, a structural zero reading slot 0 under wm = 0;
+            // the packed record in LDS at this lane's row offset wrow + col(j), a structural zero under wm = 0;
             // the records were written by the other lanes of this wave, and LDS serves a wave's accesses in order.
             // (Round 2 used two
             // buffers two stages ahead; once the control-affine sweep dropped the uu block, the second buffer's
@@ -1124,7 +1248,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             auto load_w = [&](int k, Wb& b) {
 #pragma unroll
                 for (int j = 0; j < KZ; ++j)   // row rx; masked at its uses
-                    b.r[j] = WLDS ? sW[k * PK + wofs[j]] : wH[k * HW + rx * KZ + j];
+                    b.r[j] = WLDS ? sW[k * PK + wrow + WPack<Model>::col(j)] : wH[k * HW + rx * KZ + j];
                 if constexpr (!CAFF) {
 #pragma unroll
                     for (int j = 0; j < NU * NU; ++j) b.u[j] = wH[k * HW + NX * KZ + j];
@@ -1164,7 +1288,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     u[c] = sU[k * NU + c];
                     um[c] = LAST ? up[c] : sU[(k - 1) * NU + c];
                 }
-                load_acol(k, acol);
+                load_acol(k, jcol, acol);
                 // XB: the barrier pieces of this stage (u_k) and of x_k (stage k-1), loaded with the stage operands:
                 // read at their uses, deep in the stage, their HBM latency was exposed
                 double xsgu[XB ? NU : 1], xbbu[XB ? NU : 1], xsgx = 0.0, xbbx = 0.0;
@@ -1534,6 +1658,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         [[maybe_unused]] auto backward_vec = [&]() {
             if constexpr (MEHR) {
                 const double lxm = lx ? 1.0 : 0.0;
+                [[maybe_unused]] LdsB jcol = iAcN;   // load_acol's running address
                 double pvr = Qr * (lx ? sX[N * NX + rx] - tr[(N - 1) * NX + rx] : 0.0);   // Q (x_N - r_{N-1})
                 pvr = fma(lxm, sBb[(N - 1) * NY + rx], pvr);
                 struct Rec {
@@ -1556,7 +1681,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     double hFu[FU], acol[NA];
 #pragma unroll
                     for (int i = 0; i < FU; ++i) hFu[i] = sFu[k * FU + i];
-                    load_acol(k, acol);
+                    load_acol(k, jcol, acol);
                     const double mv = pvr + o.pc;
                     double mvb[NS];
                     sfor<0, NS>([&](auto I) { mvb[I] = row_bcast<I>(mv); });
