@@ -451,15 +451,24 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // strength reduction gives every unrolled copy of a load its own induction variable)
     auto pin = [](LdsB& b) { asm volatile("" : "+v"(b)); };
     [[maybe_unused]] const LdsB iKc = shb + 8 * (int)(sKc - shm), iKz = iKc + 8 * NX;   // the block; its zero row (max(NX, NU) zeros)
-    // row r of [A - I | B]: a-lanes [hFq | hFqd | hFu] row r - NQ, q-lanes h e_{NQ+r} | 0, other lanes 0
-    [[maybe_unused]] const LdsB iAq = la ? shb + 8 * ((int)(sFq - shm) + ta * NQ) : (r < NQ ? iKc + 8 * ((NX - 1) - (NQ + r)) : iKz);
+    // row r of [A - I | B]: a-lanes [hFq | hFqd | hFu] row r - NQ, q-lanes h e_{NQ+r} | 0.
+    // MIRROR: a lane without an x row takes row 0's operands (rx = 0: the addresses of lane 0, a q-lane) in the d
+    // recursion, the adjoint and the step sweep, so it carries lane 0's chain bit for bit (same instructions, same
+    // operands, same broadcasts) and the sweeps store without a lane mask: its stores go to lane 0's address with lane
+    // 0's value.  It never reaches another group: every address is this instance's own.  (The u-lanes of the step sweep
+    // keep their own chain; see there.)  Without MIRROR such a lane reads the zero row and its stores stay masked.
+    constexpr bool MIRROR = LOPS && NQ > 0 && NQ == NA && (NA - 1) * NA < KC;   // (= ACOLP, below)
+    [[maybe_unused]] const double Qa = MIRROR ? w[rx] : Qr;   // Q of the x row whose chain the lane carries in the adjoint
+    [[maybe_unused]] const LdsB iAq =
+        la ? shb + 8 * ((int)(sFq - shm) + ta * NQ) : ((r < NQ || MIRROR) ? iKc + 8 * ((NX - 1) - (NQ + rq)) : iKz);
     [[maybe_unused]] const int zAq = la ? 8 * FQ : 0, zAd = la ? 8 * FD : 0, zBr = la ? 8 * FU : 0;
-    [[maybe_unused]] const LdsB iAd = la ? shb + 8 * ((int)(sFqd - shm) + ta * NA) : (r < NQ ? iAq + 8 * NQ : iKz);
+    [[maybe_unused]] const LdsB iAd = la ? shb + 8 * ((int)(sFqd - shm) + ta * NA) : ((r < NQ || MIRROR) ? iAq + 8 * NQ : iKz);
     [[maybe_unused]] const LdsB iBr = la ? shb + 8 * ((int)(sFu - shm) + ta * NU) : iKz;
     // column r of A's a-rows: a-lanes hFqd[:, r - NQ], q-lanes hFq[:, r], other lanes 0.  With NQ == NA both kinds of
     // column have the element stride NA, an immediate; a lane without the role reads the block from its start, where
     // the offsets t NA (t < NA) are zeros (they never meet h at NX - 1 = 2 NA - 1).  Other shapes keep the blend.
     constexpr bool ACOLP = LOPS && NQ == NA && (NA - 1) * NA < KC;
+    static_assert(!MIRROR || ACOLP, "a mirrored lane reads row 0's column through the per-lane column address");
     [[maybe_unused]] const int zAc = (la || r < NQ) ? 8 * FD : 0;
     [[maybe_unused]] const LdsB iAc = la ? shb + 8 * ((int)(sFqd - shm) + ta) : (r < NQ ? shb + 8 * ((int)(sFq - shm) + rq) : iKc),
                                 iAcN = iAc + (N - 1) * zAc;   // ... at the last stage
@@ -1042,9 +1051,11 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         // LDS operands are loaded one stage ahead and the dot products split into two partial sums.
         auto d_recursion_dist = [&]() {
             double dr = 0.0;
-            if (lx) sD[rx] = 0.0;
+            if (MIRROR || lx) sD[rx] = 0.0;   // (also what re-zeroes the step sweep's dump doubles, see step_dist)
             // stage operands (row r of A - I through the lane's own address, used as loaded; the wait for a load sits a
-            // full stage after its issue): two buffers, each refilled two stages ahead
+            // full stage after its issue): two buffers, each refilled two stages ahead.  MIRROR: a buffer is refilled
+            // after its last use in program order (the refill closes the stage, behind a scheduling barrier), so the
+            // old and the new contents are never live together and the unroll by two renames the buffers without a copy.
             struct Op {
                 double q[NQ > 0 ? NQ : 1], d[NA], c;
             };
@@ -1073,7 +1084,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 // unconditional and unclamped (static wait counts; the address is a strength-reduced increment): past
                 // the last stage the loads read the next arrays of this instance's LDS block (sFq -> sFqd -> sFu,
                 // sC -> sFq), values never used
-                fetch(k + 2, o);
+                if constexpr (!MIRROR) fetch(k + 2, o);
                 sfor<0, NX>([&](auto I) { db[I] = row_bcast<I>(dr); });
                 double t0 = dr + cr, t1 = 0.0;
 #pragma unroll
@@ -1081,10 +1092,15 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     if (j & 1) t1 = fma(arow[j], db[j], t1);
                     else t0 = fma(arow[j], db[j], t0);
                 }
-                // no lane-role mask on the chain: only the x-lanes' d is broadcast or stored, and the other lanes'
-                // finite leftovers (a sum of c_k[0]) are never read
+                // no lane-role mask on the chain: only the x-lanes' d is broadcast.  MIRROR: the other lanes carry lane 0's
+                // d and store it again over lane 0's (same address, same bits), so the store needs no exec mask;
+                // otherwise their finite leftovers (a sum of c_k[0]) are never read or stored
                 dr = t0 + t1;
-                if (lx) sD[(k + 1) * NX + rx] = dr;
+                if (MIRROR || lx) sD[(k + 1) * NX + rx] = dr;
+                if constexpr (MIRROR) {
+                    __builtin_amdgcn_sched_barrier(0);   // the refill stays behind the last use of o
+                    fetch(k + 2, o);
+                }
             };
             Op o0, o1;
             fetch(0, o0);
@@ -1123,12 +1139,15 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         // Runs before the stop test, so a converged wave skips the Riccati sweep.
         auto adjoint_dist = [&]() {
             double lamr;
+            // MIRROR: a lane without an x row carries lane 0's lam (Q, column, operands and stores of row 0), so the
+            // stores need no exec mask and lmax no lane factor (the maximum over the group sees lane 0's value twice);
+            // Qa is the Q of the row the lane carries (without MIRROR: Qr)
             {
-                const double eb = lx ? sX[N * NX + rx] - tr[(N - 1) * NX + rx] : 0.0;   // x_N - r_{N-1}
-                lamr = Qr * (sD[N * NX + rx] + eb);
-                if constexpr (XB) lamr += lxf * sZg[(N - 1) * NY + rx];   // z_u - z_l of x_N's bounds
+                const double eb = (MIRROR || lx) ? sX[N * NX + rx] - tr[(N - 1) * NX + rx] : 0.0;   // x_N - r_{N-1}
+                lamr = Qa * (sD[N * NX + rx] + eb);
+                if constexpr (XB) lamr += (MIRROR ? 1.0 : lxf) * sZg[(N - 1) * NY + rx];   // z_u - z_l of x_N's bounds
                 lmax = fmax(lmax, fabs(lamr));
-                if (lx) sD[N * NX + rx] = lamr;   // lam_k replaces d_k (read one stage earlier)
+                if (MIRROR || lx) sD[N * NX + rx] = lamr;   // lam_k replaces d_k (read one stage earlier)
             }
             // stage operands as loaded, two buffers refilled two stages ahead (d_k is read before stage k writes lam_k
             // over it): column r of A's a-rows and the pieces of Q (d_k + x_k - r_{k-1})[r], combined at the use
@@ -1138,7 +1157,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             // ACOLP: the lane's column address runs down with the fetches, one add per stage and no clamp: fetch number
             // i reads stage N - 1 - i, and the two fetches past stage 1 (values never used) read stages 0 and -1 of the
             // lane's array -- the end of the array in front of it (sC, sFq), inside the instance's block
-            [[maybe_unused]] LdsB jc = iAcN;
+            [[maybe_unused]] LdsB jc = (!MIRROR || lx) ? iAcN : shb + 8 * ((int)(sFq - shm) + (N - 1) * FD);
+            [[maybe_unused]] const int zc = MIRROR ? 8 * FD : zAc;   // (every x-lane is a q- or an a-lane)
             auto fetch = [&](int k, Op& o) {   // k >= 1
 #pragma unroll
                 for (int t2 = 0; t2 < NA; ++t2) {
@@ -1150,16 +1170,16 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     }
                 }
                 if constexpr (ACOLP) {
-                    jc -= zAc;
+                    jc -= zc;
                     pin(jc);
                 }
                 o.xk = sX[k * NX + rx];
                 o.trm = tr[(k - 1) * NX + rx];
                 o.dk = sD[k * NX + rx];
-                if constexpr (XB) o.zg = sZg[(k - 1) * NY + rx];   // z_u - z_l of x_k's bounds (masked by lxf)
+                if constexpr (XB) o.zg = sZg[(k - 1) * NY + rx];   // z_u - z_l of x_k's bounds
             };
-            // stage k >= 1: lam_k from lam_{k+1}; then refill o with stage k - 2 (k >= 3)
-            auto stage = [&](int k, Op& o) {
+            // stage k >= 1: lam_k from lam_{k+1}; then refill o with stage k - 2 (k >= 3; MIRROR: where `more` says so)
+            auto stage = [&](int k, Op& o, [[maybe_unused]] bool more = true) {
                 double acol[NA];
 #pragma unroll
                 for (int t2 = 0; t2 < NA; ++t2) {
@@ -1171,14 +1191,15 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                         acol[t2] = v;
                     }
                 }
-                double qe = Qr * (o.dk + (o.xk - o.trm));
+                double qe = Qa * (o.dk + (o.xk - o.trm));
                 if constexpr (XB) qe += o.zg;
-                fetch(k >= 3 ? k - 2 : 1, o);   // unconditional: static wait counts
+                if constexpr (!MIRROR) fetch(k >= 3 ? k - 2 : 1, o);   // unconditional: static wait counts
                 double lamb[NX];
                 sfor<0, NX>([&](auto I) { lamb[I] = row_bcast<I>(lamr); });
                 // (A^T lam)[r] + Q e_{k-1}[r], two partial sums
-                // unmasked chain: a lane without an x row has Qr = 0, acol = 0 and hq = 0, so it carries 0 (XB: a finite
-                // sum of another row's z gaps) -- never broadcast or stored, and masked out of lmax
+                // unmasked chain: a lane without an x row carries lane 0's lam (MIRROR), stored again over lane 0's;
+                // otherwise it has Qr = 0, acol = 0 and hq = 0, so it carries 0 (XB: a finite sum of another row's z
+                // gaps) -- never broadcast or stored, and masked out of lmax
                 double t0 = lamr + qe, t1 = 0.0;
 #pragma unroll
                 for (int z = 0; z < NQ; ++z) t1 = fma(hq[z], lamb[z], t1);
@@ -1188,19 +1209,42 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     else t0 = fma(acol[s2], lamb[NQ + s2], t0);
                 }
                 lamr = t0 + t1;
-                lmax = fmax(lmax, fabs(lxf * lamr));
-                if (lx) sD[k * NX + rx] = lamr;
+                lmax = fmax(lmax, fabs(MIRROR ? lamr : lxf * lamr));
+                if (MIRROR || lx) sD[k * NX + rx] = lamr;
+                if constexpr (MIRROR) {   // the refill closes the stage, behind the last use of o (no buffer copies)
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (more) fetch(k - 2, o);
+                }
             };
             if (N >= 2) {
                 Op o0, o1;
                 fetch(N - 1, o0);
                 fetch(N >= 3 ? N - 2 : 1, o1);
                 int k = N - 1;
-                for (; k >= 2; k -= 2) {
-                    stage(k, o0);
-                    stage(k - 1, o1);
+                if constexpr (MIRROR) {
+                    // no clamp: the pair loop takes the stages whose refills (k - 2, k - 3) exist, unconditionally
+                    // (static wait counts at its top); the two or three stages left run apart, stage 3 with its refill
+                    for (; k >= 4; k -= 2) {
+                        stage(k, o0);
+                        stage(k - 1, o1);
+                    }
+                    if (k == 3) {
+                        stage(3, o0);
+                        stage(2, o1, false);
+                        stage(1, o0, false);
+                    } else if (k == 2) {
+                        stage(2, o0, false);
+                        stage(1, o1, false);
+                    } else {
+                        stage(1, o0, false);
+                    }
+                } else {
+                    for (; k >= 2; k -= 2) {
+                        stage(k, o0);
+                        stage(k - 1, o1);
+                    }
+                    if (k == 1) stage(1, o0);
                 }
-                if (k == 1) stage(1, o0);
             }
             // the lam rows of the other lanes of this wave must be visible to the gradient pass
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1890,16 +1934,67 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 // K_k columns were stored by the other lanes of this wave in the backward sweep
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                constexpr bool RUN = MIRROR;   // running addresses, unmasked stores, no clamped prefetch (below)
                 double sr = 0.0;
-                if (lx) sDX[rx] = 0.0;
+                if (RUN || lx) sDX[rx] = 0.0;
                 constexpr int NK = NS + 1;
                 const double* const Kp = wK + ru * NK;   // row ru of K_k | kff_k at Kp + k NU NK
-                // operands double-buffered two stages ahead (manual unroll by two, so the buffers are renamed, not
-                // copied): the K row from the HBM/L2 workspace, row r of [A - I | B] and c_k[r] from LDS
+                // the stage operands of a buffer: the K row from the HBM/L2 workspace, row r of [A - I | B] and c_k[r]
+                // from LDS
                 struct Ops {
                     double K[NK], a[NX], b[NU], c, Rw[BOUNDED ? NR : 1];
                 };
                 const double* const Rp = wRel + ru * NR;   // BOUNDED: un-held row ru at Rp + k NU NR
+                // RUN: every address of the sweep runs along it, one add per stage, opaque to the loop optimiser -- the
+                // lane's three row addresses and its c address (the stage of the next refill), the K (and un-held) row
+                // pointer, and two store addresses:
+                //   js: where the lane's s goes -- x-lanes dx_{k+1}[r] in sDX (stride NX), u-lanes du_k in sDU (stride NU);
+                //       the stored value is the lane's next s, so one store serves both roles and s needs one select
+                //   jt: where A dx_k + B du_k goes -- x-lanes sD[k+1][r] (stride NX).  A u-lane has no such row; its sum
+                //       (finite: its own du_{k-1} plus row 0's products) goes to sD[ru] with stride 0.  sD[0 .. NX) is
+                //       d_0: no sweep or pass of the lane-distributed kernels reads it (they start at sD[NX]), and the d
+                //       recursion zeroes it again at the start of the next iteration.
+                // A lane without a role carries lane 0's chain (rows, c and K row 0 as lane 0) and stores lane 0's
+                // values to lane 0's addresses.
+                using LdsW = __attribute__((address_space(3))) double*;
+                [[maybe_unused]] LdsB ja = iAq, jd = iAd, jb = iBr, jcs = shb + 8 * ((int)(sC - shm) + rx);
+                [[maybe_unused]] LdsB js = shb + 8 * (lu ? (int)(sDU - shm) + ru : (int)(sDX - shm) + NX + rx);
+                [[maybe_unused]] LdsB jt = shb + 8 * (lu ? (int)(sD - shm) + ru : (int)(sD - shm) + NX + rx);
+                [[maybe_unused]] const int zs = lu ? 8 * NU : 8 * NX, zt = lu ? 0 : 8 * NX;
+                using GlbD = const __attribute__((address_space(1))) double*;   // (stays a global load behind the pin)
+                [[maybe_unused]] GlbD jK = (GlbD)Kp;
+                [[maybe_unused]] GlbD jR = (GlbD)Rp;
+                [[maybe_unused]] auto refill = [&](Ops& o) {   // the next stage in order
+#pragma unroll
+                    for (int j = 0; j < NK; ++j) o.K[j] = jK[j];
+#pragma unroll
+                    for (int s2 = 0; s2 < NQ; ++s2) o.a[s2] = lds(ja + 8 * s2);
+#pragma unroll
+                    for (int s2 = 0; s2 < NA; ++s2) o.a[NQ + s2] = lds(jd + 8 * s2);
+#pragma unroll
+                    for (int c = 0; c < NU; ++c) o.b[c] = lds(jb + 8 * c);
+                    o.c = lds(jcs);
+                    if constexpr (BOUNDED) {
+#pragma unroll
+                        for (int j = 0; j < NR; ++j) o.Rw[j] = jR[j];
+                    }
+                };
+                [[maybe_unused]] auto advance = [&]() {
+                    ja += zAq;
+                    jd += zAd;
+                    jb += zBr;
+                    jcs += 8 * NX;
+                    jK += NU * NK;
+                    pin(ja);
+                    pin(jd);
+                    pin(jb);
+                    pin(jcs);
+                    asm volatile("" : "+v"(jK));
+                    if constexpr (BOUNDED) {
+                        jR += NU * NR;
+                        asm volatile("" : "+v"(jR));
+                    }
+                };
                 auto fetch = [&](int k, Ops& o) {
 #pragma unroll
                     for (int j = 0; j < NK; ++j) o.K[j] = Kp[k * NU * NK + j];
@@ -1910,7 +2005,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                         for (int j = 0; j < NR; ++j) o.Rw[j] = Rp[k * NU * NR + j];
                     }
                 };
-                auto stage = [&](int k, Ops& o) {
+                // (more: RUN, whether the stage refills its buffer with the stage three ahead)
+                auto stage = [&](int k, Ops& o, [[maybe_unused]] bool more = true) {
                     double sb[NS];
                     sfor<0, NS>([&](auto I) { sb[I] = row_bcast<I>(sr); });
                     double du0 = o.K[NS], du1 = 0.0;
@@ -1928,11 +2024,21 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
 #pragma unroll
                     for (int c = 0; c < NU; ++c) ad = fma(o.b[c], dub[c], ad);
                     const double dxn = ad + o.c;
-                    if (lx) {
-                        sDX[(k + 1) * NX + rx] = dxn;
-                        sD[(k + 1) * NX + rx] = ad;
+                    if constexpr (RUN) {   // unmasked stores through the lane's running store addresses
+                        sr = lu ? du : dxn;
+                        *(LdsW)js = sr;
+                        *(LdsW)jt = ad;
+                        js += zs;
+                        jt += zt;
+                        pin(js);
+                        pin(jt);
+                    } else {
+                        if (lx) {
+                            sDX[(k + 1) * NX + rx] = dxn;
+                            sD[(k + 1) * NX + rx] = ad;
+                        }
+                        if (lu) sDU[k * NU + ru] = du;
                     }
-                    if (lu) sDU[k * NU + ru] = du;
                     if constexpr (BOUNDED) {
                         if (check && lu) {
                             const double hv = sHold[k * NU + ru], t = sU[k * NU + ru] + du;
@@ -1954,13 +2060,59 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                             }
                         }
                     }
-                    sr = lx ? dxn : (lu ? du : 0.0);
-                    fetch(k + 3 < N ? k + 3 : N - 1, o);   // unconditional: static wait counts
+                    if constexpr (RUN) {
+                        if (more) {
+                            refill(o);
+                            advance();
+                        }
+                    } else {
+                        sr = lx ? dxn : (lu ? du : 0.0);
+                        fetch(k + 3 < N ? k + 3 : N - 1, o);   // unconditional: static wait counts
+                    }
                 };
                 // three buffers, refilled three stages ahead: the K rows come from L2/MALL (the workspace of a
                 // 512-instance XCD exceeds its 4 MB L2) and one stage of the sweep (~300 cycles) did not cover that
                 // latency -- with two buffers every stage waited for the loads issued one stage earlier
                 Ops o0, o1, o2;
+                if constexpr (RUN) {
+                    // No clamp and no read past stage N - 1.  The N - 3 stages that have a stage three ahead refill their
+                    // buffer: the three-stage body takes them three at a time (the same outstanding loads on every path
+                    // at its top: the wait before stage k's operands is vmcnt(#loads of stages k + 1, k + 2)), the one
+                    // or two left over follow it; the last three stages run without a refill, from the buffers the
+                    // rotation has reached.  The opening loads of a horizon shorter than three read its last stage
+                    // again (values never used) instead of moving on.
+                    refill(o0);
+                    if (N > 1) advance();
+                    refill(o1);
+                    if (N > 2) advance();
+                    refill(o2);
+                    advance();
+                    int k = 0;
+                    for (; k + 5 < N; k += 3) {
+                        stage(k, o0, true);
+                        stage(k + 1, o1, true);
+                        stage(k + 2, o2, true);
+                    }
+                    const int left = N - 3 - k;   // refilling stages left: 0, 1 or 2 (negative: N < 3)
+                    if (left == 1) {
+                        stage(k, o0, true);
+                        stage(k + 1, o1, false);
+                        stage(k + 2, o2, false);
+                        stage(k + 3, o0, false);
+                    } else if (left == 2) {
+                        stage(k, o0, true);
+                        stage(k + 1, o1, true);
+                        stage(k + 2, o2, false);
+                        stage(k + 3, o0, false);
+                        stage(k + 4, o1, false);
+                    } else {
+                        stage(k, o0, false);
+                        if (N >= 2) stage(k + 1, o1, false);
+                        if (N >= 3) stage(k + 2, o2, false);
+                    }
+                    return;
+                }
+                // (the other models: the clamped prefetch, N mod 3 stages peeled in front)
                 fetch(0, o0);
                 fetch(N > 1 ? 1 : 0, o1);
                 fetch(N > 2 ? 2 : 0, o2);

@@ -15,17 +15,20 @@ i = s.index(name + ":")
 lines = s[i:s.index(".Lfunc_end", i)].split("\n")
 loops = collections.OrderedDict()
 cur = None
+last = None   # the last block label: a nested single-block loop names its own header on the line after its label
 for l in lines:
     m = re.search(r"(?:Header=BB(\S+) Depth=(\d))|(?:This (?:Inner )?Loop Header: Depth=(\d))", l)
     lab = re.match(r"^(\.LBB(\S+)):", l) or re.match(r"^; %bb", l)
-    if lab or (l.startswith(";") and "Loop Header" in l):
+    if lab or (l.lstrip().startswith(";") and "Loop Header" in l):
+        lm = re.match(r"^\.LBB(\S+):", l)
         if m and m.group(1):
             cur = ("BB" + m.group(1), m.group(2))
         elif m and m.group(3):
-            lm = re.match(r"^\.LBB(\S+):", l)
-            cur = ("BB" + lm.group(1), m.group(3)) if lm else cur
+            cur = ("BB" + lm.group(1), m.group(3)) if lm else (("BB" + last, m.group(3)) if last else cur)
         elif lab:
             cur = None
+        if lm:
+            last = lm.group(1)
         continue
     if cur and l.startswith("\t") and not l.strip().startswith(";") and not l.strip().startswith("."):
         loops.setdefault(cur, []).append(l.strip())
