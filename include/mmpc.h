@@ -387,7 +387,8 @@ int mmpc_solve_batch_host_pinned(mmpc_handle* h, int64_t B, const double* x0, co
  *             run the same operations per instance and agree to rounding, not bit for bit.
  *   gain_status   [B] or NULL.
  * Refused with MMPC_ERR_UNSUPPORTED, never run under another meaning: a linear-mode model; a handle with any finite
- * state bound (barrier-smoothed sensitivities are another feature).  n_gain outside 1..N, n_pin outside 0..N-1, a bad
+ * state bound whose sensitivity barrier is off (mmpc_set_sensitivity_barrier below; off is the state of every new
+ * handle).  n_gain outside 1..N, n_pin outside 0..N-1, a bad
  * bounds_stride, an unknown hessian or kernel: MMPC_ERR_INVALID_ARG, mmpc_last_error names the argument.  Everything is
  * checked from the arguments alone before any device call; B = 0 is a no-op success.
  * mmpc_feedback_gains_batch takes DEVICE pointers, is stream-ordered on `stream`, never synchronises and never
@@ -451,13 +452,14 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
  * Backward-only mode: when traj_bar, weights_bar and adj_V are all NULL no record is stored, no forward sweep runs and
  * workspace may be NULL; x0_bar and u_prev_bar are bit for bit those of the full call.  Otherwise a workspace that is
  * NULL or smaller than the query: MMPC_ERR_INVALID_ARG naming `workspace` / `workspace_bytes`.
- * Refused with MMPC_ERR_UNSUPPORTED: a linear-mode model; a handle with any finite state bound.  n_pin outside 0..N-1,
+ * Refused with MMPC_ERR_UNSUPPORTED: a linear-mode model; a handle with any finite state bound whose sensitivity
+ * barrier is off (mmpc_set_sensitivity_barrier below).  n_pin outside 0..N-1,
  * a bad bounds_stride or weights_stride, an unknown hessian, a NULL V_bar: MMPC_ERR_INVALID_ARG, mmpc_last_error names
  * the argument.  Everything is checked from the arguments alone before any device call; B = 0 is a no-op success.
  * mmpc_solve_vjp_batch takes DEVICE pointers and is one stream-ordered launch on `stream` that never synchronises and
  * never allocates (the handle's workspace is not used; mmpc_reserve_workspace's sizes are unchanged), so it can be
  * captured in a hipGraph.  mmpc_solve_vjp_batch_host takes host pointers, stages them, brings its own workspace and is
- * synchronous.  Multi-device and RCCL entries, state-bounded handles, a 16-lane kernel: out of scope. */
+ * synchronous.  Multi-device and RCCL entries, a 16-lane kernel: out of scope. */
 int mmpc_solve_vjp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes);
 int mmpc_solve_vjp_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
                          const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
@@ -469,6 +471,48 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
                               int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian,
                               double* x0_bar, double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V,
                               int32_t* vjp_status);
+
+/* ---- feedback gains and solve VJP of a state-bounded handle: the sensitivity barrier (additive to ABI 6) ----
+ * A state-bounded solve is an interior-point solve: the V it returns lies strictly inside every bound, near the
+ * central path of its last barrier value.  Its sensitivity is the recursion of the two definitions above with the
+ * barrier's Hessian on the diagonal of the bounded rows and the barrier's gradient in the multiplier recursion.
+ *
+ * Definition.  Notation of the gain and VJP comments; for a handle with at least one finite state bound and the
+ * sensitivity barrier switched on, with parameters mu_s > 0 and sigma_cap > 0:
+ *   Bounded variables are those the interior-point solve bounds: x_{k+1} for k = 0..N-1 under the handle's state
+ *   bounds, u_k under u_lb / u_ub / bounds_stride of the call; |b| >= 1e19 is infinite.  x_0 has no term.  Controls of
+ *   stages k < n_pin are held exactly as above and get no term.  No control is held by bit-equality on such a handle:
+ *   the interior point never returns a control on its bound.
+ *   Per bounded entry y with slacks s_l = y - l, s_u = u - y (a side whose bound is infinite contributes nothing):
+ *     beta = 2 mu_s (1 / s_u - 1 / s_l),   D = min(2 mu_s (1 / s_l^2 + 1 / s_u^2), sigma_cap)
+ *   (the J scale: the barrier objective is J - 2 mu sum log s).
+ *   Multipliers: lam_{N-1} = beta(x_N), lam_{k-1} = A_k^T nu_k + beta(x_k), nu_k = 2 Q e_k + lam_k; W_k uses these
+ *   nu_k; Gauss-Newton ignores beta.
+ *   Recursion: P_{k+1}[x, x] += diag D(x_{k+1}) before T^T P_{k+1} T is formed; M_uu += diag D(u_k) on the controls
+ *   not pinned; everything else is as written above.  The VJP's q, kff, p, its forward sweep and its output formulas
+ *   are unchanged: the barrier term does not depend on theta.
+ *   Status: a bounded entry with a slack that is <= 0 or not finite gives the instance status 2, with the all-zero /
+ *   neighbours-untouched rules above.  The Gauss-Newton fallback (status 1) is unchanged.
+ * Meaning: the derivative of the mu_s-barrier problem's solution at the V given.  With mu_s the barrier value the solve
+ * ended at, that is the derivative of the solve's own map.  mmpc_sensitivity_barrier_default returns the value the
+ * monotone rule reaches first with 2 mu <= its complementarity tolerance (2.5e-9, computed from the solver's
+ * schedule) and sigma_cap = 1e12.  Caveat: an instance that needed a further decrease of mu ends at the floor 5e-10,
+ * and Mehrotra's rule ends at a per-instance value; for those the multipliers in W_k are an estimate, and mu_s is the
+ * caller's to set.  sigma_cap bounds the condition of the recursion (the slacks of an active bound reach 1e-12, D
+ * 1e16) and is part of the meaning: against central differences of the solve the gains agree to 5e-7 at 1e12 and
+ * without a cap, to 5e-5 at 1e10, and not at all at 1e6, a value for checking the arithmetic only.
+ *
+ * mmpc_set_sensitivity_barrier: mu = 0 switches the barrier off (the state of every new handle: the gain and VJP calls
+ * refuse a state-bounded handle), mu > 0 switches it on.  A non-finite or negative mu, a sigma_cap that is <= 0 or NaN:
+ * MMPC_ERR_INVALID_ARG naming the argument; sigma_cap = +inf is allowed (no cap).  On a handle without a finite state
+ * bound the setting has no effect at all.  With it on, mmpc_feedback_gains_batch[_host] and
+ * mmpc_solve_vjp_batch[_host] accept the handle with the same signatures and launch rules (no allocation, no
+ * synchronisation, hipGraph capture; mmpc_solve_vjp_workspace_bytes and mmpc_reserve_workspace unchanged); the
+ * 16-lane gain kernel's stage records grow by 2 nx + nu doubles, and its availability and the AUTO rule are evaluated
+ * with that size.  Gradients with respect to the bounds, a per-instance mu_s: out of scope. */
+int mmpc_sensitivity_barrier_default(double* mu, double* sigma_cap);
+int mmpc_set_sensitivity_barrier(mmpc_handle* h, double mu, double sigma_cap);
+int mmpc_get_sensitivity_barrier(const mmpc_handle* h, double* mu, double* sigma_cap);
 
 /* Continuous-time linearisation at (x[b], u[b]): A = df/dx [nx*nx], B = df/du [nx*nu]
  * column-major, xdot = f(x,u) [nx].  DEVICE pointers; any output may be NULL. */

@@ -48,17 +48,28 @@ __host__ __device__ constexpr int64_t adjoint_lane_doubles(int nx, int nu, int N
     return (int64_t)N * adjoint_rec_doubles(nx, nu);
 }
 
+// the XB instantiations' parameters: AdjointParams plus the sensitivity barrier's tail (gain_sweep.h); AdjointParams
+// itself, and with it the other instantiations' kernel arguments, stays as it is
+struct AdjointXbParams : AdjointParams {
+    XbTail xb;
+};
+template <bool XB>
+using AdjointParamsOf = std::conditional_t<XB, AdjointXbParams, AdjointParams>;
+
 // One lane per instance, both sweeps in one launch.  The backward sweep is gain_lane_kernel's fused stage (restated
 // here, that kernel is left as it is) plus q, kff and p; with a workspace it stores G_k | kff_k per stage, element i of
 // lane l of workgroup g at ws[(g * doubles per lane + i) * 64 + l], so a wave's store of one element is one 512-byte
 // line.  The forward sweep evaluates value and Jacobian again per stage (nothing of [A | B] is stored), reads the
 // record back, writes adj_V and traj_bar per stage and keeps the nx + 2 nu weight sums in registers.  A second pass
-// over both sweeps runs only for the Gauss-Newton fallback.
-template <class Model, bool EXACT, bool BOUNDED>
-__global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParams p) {
+// over both sweeps runs only for the Gauss-Newton fallback.  XB: the sensitivity barrier's terms join the backward
+// stage as in gain_lane_kernel (XbTail, gain_sweep.h); q, kff, p, the forward sweep and the outputs are the same text,
+// the barrier does not depend on theta.
+template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
+__global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParamsOf<XB> p) {
     constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU, NQ = Model::NQ, NA = NX - NQ, NP = K * (K + 1) / 2;
     constexpr int RD = NU * (K + 1);
     static_assert(!EXACT || HasHess<Model>::value, "the exact adjoint needs Model::eval_hess");
+    static_assert(!XB || BOUNDED, "the XB instantiations read the control bounds");
     const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (b >= p.B) return;
     const int N = p.N;
@@ -117,6 +128,24 @@ __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParams p)
             for (int c = 0; c < NU; ++c) u[c] = v[k * K + NX + c];
             model_eval_jac<Model>(x, u, xd, fx, fu);
             double J[NX][K], nuk[NX], chk = 0.0;   // J = [A_k | B_k]
+            [[maybe_unused]] double Du[NU];
+            if constexpr (XB) {   // lam_k gets beta(x_{k+1}), P_{k+1} gets D(x_{k+1}) in place; D(u_k) for M_uu
+                bool in = true;
+#pragma unroll
+                for (int r = 0; r < NX; ++r) {
+                    double be, D;
+                    in = xb_terms(v[(k + 1) * K + r], p.xb.x_lb[r], p.xb.x_ub[r], p.xb.mu, p.xb.cap, be, D) && in;
+                    lam[r] += be;
+                    P[gain_sym(r, r, K)] += D;
+                }
+#pragma unroll
+                for (int c = 0; c < NU; ++c) {
+                    double be;
+                    Du[c] = 0.0;
+                    if (k >= p.n_pin) in = xb_terms(u[c], lb[c], ub[c], p.xb.mu, p.xb.cap, be, Du[c]) && in;
+                }
+                chk += in ? 0.0 : NAN;
+            }
 #pragma unroll
             for (int r = 0; r < NX; ++r) {
 #pragma unroll
@@ -171,12 +200,13 @@ __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParams p)
             double Muu[NU][NU], Mus[NU][K], il[NU];
             bool held[NU];
 #pragma unroll
-            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED>(k, p.n_pin, u[c], lb[c], ub[c]);
+            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED && !XB>(k, p.n_pin, u[c], lb[c], ub[c]);
 #pragma unroll
             for (int c = 0; c < NU; ++c) {
 #pragma unroll
                 for (int d = 0; d < NU; ++d) {
-                    const double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    if constexpr (XB) m += c == d ? Du[c] : 0.0;
                     Muu[c][d] = (held[c] || held[d]) ? (c == d ? 1.0 : 0.0) : m;
                 }
 #pragma unroll

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "models.h"
 #include "sqp_group.h"
@@ -43,6 +44,43 @@ struct GainParams {
     int32_t* status;        // [B] or null: 0 as asked, 1 Gauss-Newton fallback, 2 failed (gains 0)
     int gpw;                // 16-lane kernel: instances per workgroup (<= kGroupsPerWave)
 };
+
+// The sensitivity barrier of a state-bounded handle (mmpc_set_sensitivity_barrier, include/mmpc.h): the
+// XB instantiations take GainParams plus this tail, so the kernel arguments of every other instantiation stay as
+// they are.  With y a bounded entry (x_{k+1} under x_lb / x_ub, u_k of a stage k >= n_pin under u_lb / u_ub), slacks
+// s_l = y - l, s_u = u - y:  beta = 2 mu (1 / s_u - 1 / s_l),  D = min(2 mu (1 / s_l^2 + 1 / s_u^2), cap);  then
+//   lam_{N-1} = beta(x_N), lam_{k-1} = A_k^T nu_k + beta(x_k),  P_{k+1}[x, x] += diag D(x_{k+1}) before M_yy is formed,
+//   M_uu += diag D(u_k);  no control is held by bit-equality (the interior point returns none on its bound).
+struct XbTail {
+    double x_lb[16], x_ub[16];   // |b| >= 1e19 is infinite
+    double mu, cap;
+};
+struct GainXbParams : GainParams {
+    XbTail xb;
+};
+template <bool XB>
+using GainParamsOf = std::conditional_t<XB, GainXbParams, GainParams>;
+
+// beta and D of one entry y under (l, u); false when a slack of a finite side is <= 0 or not finite
+__device__ __forceinline__ bool xb_terms(double y, double l, double u, double mu, double cap, double& beta, double& D) {
+    bool ok = true;
+    double d = 0.0;
+    beta = 0.0;
+    if (u < 1e19) {
+        const double s = u - y;
+        ok = ok && s > 0.0 && s < INFINITY;
+        beta += 2.0 * mu / s;
+        d += 2.0 * mu / (s * s);
+    }
+    if (l > -1e19) {
+        const double s = y - l;
+        ok = ok && s > 0.0 && s < INFINITY;
+        beta -= 2.0 * mu / s;
+        d += 2.0 * mu / (s * s);
+    }
+    D = fmin(d, cap);
+    return ok;
+}
 
 // index of (i, j) in the packed upper triangle of a symmetric n x n matrix
 __host__ __device__ constexpr int gain_sym(int i, int j, int n) {
@@ -104,11 +142,12 @@ __device__ __forceinline__ bool gain_held(int k, int n_pin, double u, double lb,
 
 // One lane per instance: a single fused backward sweep -- Jacobian, nu / lam, W_k, the stage step and the store of
 // G_k for k < n_gain per stage.  No workspace: the only traffic is V, the targets and G.  A second pass runs only
-// for the Gauss-Newton fallback.
-template <class Model, bool EXACT, bool BOUNDED>
-__global__ __launch_bounds__(64) void gain_lane_kernel(const GainParams p) {
+// for the Gauss-Newton fallback.  XB: the sensitivity barrier's terms join the stage (XbTail).
+template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
+__global__ __launch_bounds__(64) void gain_lane_kernel(const GainParamsOf<XB> p) {
     constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU, NQ = Model::NQ, NA = NX - NQ, NP = K * (K + 1) / 2;
     static_assert(!EXACT || HasHess<Model>::value, "exact gains need Model::eval_hess");
+    static_assert(!XB || BOUNDED, "the XB instantiations read the control bounds");
     const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (b >= p.B) return;
     const int N = p.N;
@@ -153,6 +192,24 @@ __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParams p) {
             for (int c = 0; c < NU; ++c) u[c] = v[k * K + NX + c];
             model_eval_jac<Model>(x, u, xd, fx, fu);
             double J[NX][K], nuk[NX], chk = 0.0;   // J = [A_k | B_k]
+            [[maybe_unused]] double Du[NU];
+            if constexpr (XB) {   // lam_k gets beta(x_{k+1}), P_{k+1} gets D(x_{k+1}) in place; D(u_k) for M_uu
+                bool in = true;
+#pragma unroll
+                for (int r = 0; r < NX; ++r) {
+                    double be, D;
+                    in = xb_terms(v[(k + 1) * K + r], p.xb.x_lb[r], p.xb.x_ub[r], p.xb.mu, p.xb.cap, be, D) && in;
+                    lam[r] += be;
+                    P[gain_sym(r, r, K)] += D;
+                }
+#pragma unroll
+                for (int c = 0; c < NU; ++c) {
+                    double be;
+                    Du[c] = 0.0;
+                    if (k >= p.n_pin) in = xb_terms(u[c], lb[c], ub[c], p.xb.mu, p.xb.cap, be, Du[c]) && in;
+                }
+                chk += in ? 0.0 : NAN;
+            }
 #pragma unroll
             for (int r = 0; r < NX; ++r) {
 #pragma unroll
@@ -207,12 +264,13 @@ __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParams p) {
             double Muu[NU][NU], Mus[NU][K], il[NU];
             bool held[NU];
 #pragma unroll
-            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED>(k, p.n_pin, u[c], lb[c], ub[c]);
+            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED && !XB>(k, p.n_pin, u[c], lb[c], ub[c]);
 #pragma unroll
             for (int c = 0; c < NU; ++c) {
 #pragma unroll
                 for (int d = 0; d < NU; ++d) {
-                    const double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    if constexpr (XB) m += c == d ? Du[c] : 0.0;
                     Muu[c][d] = (held[c] || held[d]) ? (c == d ? 1.0 : 0.0) : m;
                 }
 #pragma unroll
@@ -260,19 +318,21 @@ __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParams p) {
 
 // ---- 16 lanes per instance ----
 // LDS doubles per stage record: [A_k | B_k] (nx x K), nu_k (nx; 2 Q e_k until the lam recursion has passed), the held
-// controls of the stage as a bit mask, and with the exact Hessian W_k (K x K)
-__host__ __device__ constexpr int gain_group_rec_doubles(int nx, int nu, bool exact) {
-    return nx * (nx + nu) + nx + 1 + (exact ? (nx + nu) * (nx + nu) : 0);
+// controls of the stage as a bit mask, with the exact Hessian W_k (K x K), and with the sensitivity barrier
+// beta(x_{k+1}) (nx), D(x_{k+1}) (nx) and D(u_k) (nu)
+__host__ __device__ constexpr int gain_group_rec_doubles(int nx, int nu, bool exact, bool xb = false) {
+    return nx * (nx + nu) + nx + 1 + (exact ? (nx + nu) * (nx + nu) : 0) + (xb ? 2 * nx + nu : 0);
 }
 // LDS doubles per instance: N stage records, then the exchange area of the Riccati sweep (the rows of P C, K x K, and
 // the u rows of M_yy, nu x K)
-__host__ __device__ constexpr int gain_group_lds_doubles(int nx, int nu, int N, bool exact) {
-    return N * gain_group_rec_doubles(nx, nu, exact) + (nx + nu) * (nx + nu) + nu * (nx + nu);
+__host__ __device__ constexpr int gain_group_lds_doubles(int nx, int nu, int N, bool exact, bool xb = false) {
+    return N * gain_group_rec_doubles(nx, nu, exact, xb) + (nx + nu) * (nx + nu) + nu * (nx + nu);
 }
 
 // 16 lanes per instance, p.gpw (<= kGroupsPerWave) instances per one-wave workgroup: the partition of the 16-lane
 // solver, for batches that do not fill the device with one lane each (nx + nu < 16).
-//   A. stage-parallel (lane = stage mod 16): [A_k | B_k], 2 Q e_k and the held mask of every stage, into LDS;
+//   A. stage-parallel (lane = stage mod 16): [A_k | B_k], 2 Q e_k and the held mask of every stage, into LDS (XB: and
+//      the barrier terms of x_{k+1} and u_k; a slack that is <= 0 or not finite fails the instance);
 //   B. the serial lam recursion, component r on lane r: one nx x nx mat-vec per stage through LDS;
 //   C. stage-parallel: W_k (exact Hessian);
 //   D. the serial Riccati sweep, column j of P, M_yy and G on lane j < K.  Lane j forms row j of P C; the rows are
@@ -283,18 +343,20 @@ __host__ __device__ constexpr int gain_group_lds_doubles(int nx, int nu, int N, 
 // Lanes of a group run in lock step within their wave, so the LDS exchanges need only the compiler-level wave barrier,
 // as in sqp_group.h.
 extern __shared__ double gain_group_lds[];
-template <class Model, bool EXACT, bool BOUNDED>
-__global__ __launch_bounds__(64) void gain_group_kernel(const GainParams p) {
+template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
+__global__ __launch_bounds__(64) void gain_group_kernel(const GainParamsOf<XB> p) {
     constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU, NQ = Model::NQ, NA = NX - NQ, G = kGroupLanes;
     static_assert(K < G, "the 16-lane gain kernel holds one column of P per lane");
     static_assert(!EXACT || HasHess<Model>::value, "exact gains need Model::eval_hess");
-    constexpr int RS = gain_group_rec_doubles(NX, NU, EXACT), OJ = 0, ONU = NX * K, OH = ONU + NX, OW = OH + 1;
+    static_assert(!XB || BOUNDED, "the XB instantiations read the control bounds");
+    constexpr int RS = gain_group_rec_doubles(NX, NU, EXACT, XB), OJ = 0, ONU = NX * K, OH = ONU + NX, OW = OH + 1;
+    [[maybe_unused]] constexpr int OBE = OW + (EXACT ? K * K : 0), ODX = OBE + NX, ODU = ODX + NX;
     const int grp = threadIdx.x / G, l = threadIdx.x % G;
     const int64_t b = blockIdx.x * (int64_t)p.gpw + grp;
     if (grp >= p.gpw || b >= p.B) return;
     const int N = p.N;
     const double h = p.h;
-    double* const rec = gain_group_lds + (size_t)grp * gain_group_lds_doubles(NX, NU, N, EXACT);
+    double* const rec = gain_group_lds + (size_t)grp * gain_group_lds_doubles(NX, NU, N, EXACT, XB);
     double* const sX = rec + (size_t)N * RS;
     double* const sMu = sX + K * K;
     const int64_t NV = (int64_t)NX * (N + 1) + (int64_t)NU * N;
@@ -336,8 +398,22 @@ __global__ __launch_bounds__(64) void gain_group_kernel(const GainParams p) {
         }
         int hm = 0;
 #pragma unroll
-        for (int c = 0; c < NU; ++c) hm |= gain_held<BOUNDED>(k, p.n_pin, u[c], lb[c], ub[c]) ? (1 << c) : 0;
+        for (int c = 0; c < NU; ++c) hm |= gain_held<BOUNDED && !XB>(k, p.n_pin, u[c], lb[c], ub[c]) ? (1 << c) : 0;
         rk[OH] = static_cast<double>(hm);
+        if constexpr (XB) {
+            bool in = true;
+#pragma unroll
+            for (int r = 0; r < NX; ++r)
+                in = xb_terms(v[(k + 1) * K + r], p.xb.x_lb[r], p.xb.x_ub[r], p.xb.mu, p.xb.cap, rk[OBE + r],
+                              rk[ODX + r]) && in;
+#pragma unroll
+            for (int c = 0; c < NU; ++c) {
+                double be;
+                rk[ODU + c] = 0.0;
+                if (k >= p.n_pin) in = xb_terms(u[c], lb[c], ub[c], p.xb.mu, p.xb.cap, be, rk[ODU + c]) && in;
+            }
+            fin += in ? 0.0 : NAN;
+        }
     }
     __builtin_amdgcn_wave_barrier();
     // ---- B ----
@@ -347,6 +423,7 @@ __global__ __launch_bounds__(64) void gain_group_kernel(const GainParams p) {
         for (int k = N - 1; k >= 0; --k) {
             double* const rk = rec + (size_t)k * RS;
             if (l < NX) {
+                if constexpr (XB) lam += rk[OBE + l];   // lam_k = A_{k+1}^T nu_{k+1} + beta(x_{k+1})
                 rk[ONU + l] += lam;
                 fin += gain_nonfinite(rk[ONU + l]);   // a non-finite target fails the instance under either Hessian
             }
@@ -391,6 +468,10 @@ __global__ __launch_bounds__(64) void gain_group_kernel(const GainParams p) {
         for (int k = N - 1; k >= 0 && ok; --k) {
             const double* const rk = rec + (size_t)k * RS;
             const double* const J = rk + OJ;
+            if constexpr (XB) {   // P_{k+1}[x, x] += diag D(x_{k+1}), in place before the products
+#pragma unroll
+                for (int i = 0; i < NX; ++i) P[i] += i == j ? rk[ODX + i] : 0.0;
+            }
             __builtin_amdgcn_wave_barrier();   // the exchange area is free: every lane has read the last stage's
 #pragma unroll
             for (int c = 0; c < K; ++c) {      // row j of P C
@@ -426,7 +507,8 @@ __global__ __launch_bounds__(64) void gain_group_kernel(const GainParams p) {
                 const bool hc = (hm >> c) & 1;
 #pragma unroll
                 for (int d = 0; d < NU; ++d) {
-                    const double e = sMu[c * K + NX + d] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    double e = sMu[c * K + NX + d] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
+                    if constexpr (XB) e += c == d ? rk[ODU + c] : 0.0;
                     Muu[c][d] = (hc || ((hm >> d) & 1)) ? (c == d ? 1.0 : 0.0) : e;
                 }
                 m[c] = hc ? 0.0 : (j < NX ? M[NX + c] : (j == NX + c ? -2.0 * R[c] : 0.0));

@@ -90,6 +90,9 @@ struct mmpc_handle {
     bool x_bounded = false;
     // barrier rule of the interior point (mmpc_set_barrier_rule, MMPC_BARRIER_RULE at creation); read with the bounds
     int barrier_rule = MMPC_BARRIER_MONOTONE;
+    // sensitivity barrier of the gain and VJP calls (mmpc_set_sensitivity_barrier): sens_mu = 0 is off; read with the
+    // bounds
+    double sens_mu = 0.0, sens_cap = 1e12;
     std::mutex xb_mu;
 };
 
@@ -1288,6 +1291,36 @@ int ensure_host_ctx(mmpc_handle* h, size_t bytes) {
     return MMPC_OK;
 }
 
+// ---- sensitivity barrier of the gain and VJP calls (mmpc_set_sensitivity_barrier) ----
+constexpr double kSensCapDefault = 1e12;
+// the barrier value the monotone schedule of sqp_wave.h reaches first with 2 mu <= kIpTolCompl: where a state-bounded
+// solve under the monotone rule ends unless an instance needed one more decrease
+double sens_mu_default() {
+    double mu = kIpMu0;
+    while (2.0 * mu > kIpTolCompl)
+        mu = std::fmax(kIpTolCompl / 20.0, std::fmin(kIpKappaMu * mu, std::pow(mu, kIpThetaMu)));
+    return mu;
+}
+// What a gain or VJP call does about the handle's state bounds, read under their lock: xb->mu = 0 without a finite
+// state bound (the setting has no effect there), the bounds and the barrier with one and the barrier on; with one
+// and the barrier off the call is refused.
+int read_sens_barrier(mmpc_handle* h, const char* what, XbTail* xb) {
+    std::lock_guard<std::mutex> lk(h->xb_mu);
+    *xb = XbTail{};
+    if (!h->x_bounded) return MMPC_OK;
+    if (!(h->sens_mu > 0.0))
+        return fail(MMPC_ERR_UNSUPPORTED, std::string(what) + " not available with finite state bounds "
+                                          "(barrier-smoothed sensitivities are not computed) unless the sensitivity "
+                                          "barrier is switched on (mmpc_set_sensitivity_barrier)");
+    for (int i = 0; i < 16; ++i) {
+        xb->x_lb[i] = i < h->info.num_x ? h->x_lb[i] : -INFINITY;
+        xb->x_ub[i] = i < h->info.num_x ? h->x_ub[i] : INFINITY;
+    }
+    xb->mu = h->sens_mu;
+    xb->cap = h->sens_cap;
+    return MMPC_OK;
+}
+
 // ---- feedback gains (mmpc_feedback_gains_batch; gain_sweep.h) ----
 struct GainArgs {
     int64_t B = 0;
@@ -1301,15 +1334,16 @@ struct GainArgs {
     hipStream_t stream = nullptr;
 };
 // instances per workgroup of the 16-lane gain kernel: as many as fit 160 KB of LDS, 0 when one does not
-int gain_group_gpw(const mmpc_model_info& mi, bool exact) {
-    const size_t inst = static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, exact)) *
-                        sizeof(double);
+int gain_group_gpw(const mmpc_model_info& mi, bool exact, bool xb) {
+    const size_t inst =
+        static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, exact, xb)) *
+        sizeof(double);
     return static_cast<int>(std::min<size_t>(kGroupsPerWave, kMaxGroupLds / inst));
 }
 // The one check of a gain call's arguments: pure arithmetic on the arguments and the handle, before any device call.
 // *exact: the Hessian the call runs (AUTO: exact wherever the model has second derivatives -- the true derivative is
-// wanted whatever Hessian the solve ran, so this is not resolve_hessian).
-int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact) {
+// wanted whatever Hessian the solve ran, so this is not resolve_hessian).  *xb: read_sens_barrier's answer.
+int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact, XbTail* xb) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     const mmpc_model_info& mi = h->info;
     const int N = mi.num_shooting_nodes;
@@ -1327,12 +1361,7 @@ int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact) {
         return fail(MMPC_ERR_INVALID_ARG, "kernel: not an mmpc_gain_kernel value (" + std::to_string(a.kernel) + ")");
     if (mi.is_linear)
         return fail(MMPC_ERR_UNSUPPORTED, "feedback gains are not available for a linear-mode model");
-    {
-        std::lock_guard<std::mutex> lk(h->xb_mu);
-        if (h->x_bounded)
-            return fail(MMPC_ERR_UNSUPPORTED, "feedback gains are not available with finite state bounds "
-                                              "(barrier-smoothed sensitivities are not computed)");
-    }
+    if (int rc = read_sens_barrier(h, "feedback gains are", xb)) return rc;
     bool has_hess = false;
     with_model(mi.model_id, [&](auto* m) {
         has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
@@ -1344,7 +1373,7 @@ int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact) {
     if (a.kernel == MMPC_GAIN_KERNEL_GROUP) {
         if (mi.num_x + mi.num_u >= kGroupLanes)
             return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel) needs nx + nu < 16");
-        if (gain_group_gpw(mi, *exact) < 1)
+        if (gain_group_gpw(mi, *exact, xb->mu > 0.0) < 1)
             return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel): the stage records of one instance "
                                               "exceed 160 KB of LDS at this horizon");
     }
@@ -1364,18 +1393,18 @@ int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact) {
 // B = 256, 1.21 against 1.08 at 1024): the lane kernel's time is flat in B up to 16384 instances, the 16-lane kernel's
 // grows with the workgroups a CU has to take.  (The first rule, 16 B lanes within four waves per SIMD, was B <= 64 per
 // CU.)
-int resolve_gain_kernel(const mmpc_handle* h, int64_t B, bool exact, int kernel) {
+int resolve_gain_kernel(const mmpc_handle* h, int64_t B, bool exact, bool xb, int kernel) {
     if (kernel != MMPC_GAIN_KERNEL_AUTO) return kernel;
     const mmpc_model_info& mi = h->info;
-    const int gpw = mi.num_x + mi.num_u < kGroupLanes ? gain_group_gpw(mi, exact) : 0;
+    const int gpw = mi.num_x + mi.num_u < kGroupLanes ? gain_group_gpw(mi, exact, xb) : 0;
     return gpw >= 1 && B <= 2LL * gpw * h->cu_count ? MMPC_GAIN_KERNEL_GROUP : MMPC_GAIN_KERNEL_LANE;
 }
-template <class M, bool EXACT, bool BOUNDED>
-int launch_gain_kernels(int kernel, const GainParams& p, size_t lds, hipStream_t stream) {
+template <class M, bool EXACT, bool BOUNDED, bool XB = false>
+int launch_gain_kernels(int kernel, const GainParamsOf<XB>& p, size_t lds, hipStream_t stream) {
     if (kernel == MMPC_GAIN_KERNEL_LANE) {
-        gain_lane_kernel<M, EXACT, BOUNDED><<<grid1d(p.B, 64), 64, 0, stream>>>(p);
+        gain_lane_kernel<M, EXACT, BOUNDED, XB><<<grid1d(p.B, 64), 64, 0, stream>>>(p);
     } else if constexpr (M::NX + M::NU < kGroupLanes) {
-        auto* const k = &gain_group_kernel<M, EXACT, BOUNDED>;
+        auto* const k = &gain_group_kernel<M, EXACT, BOUNDED, XB>;
         if (lds > 64 * 1024)   // gfx950: up to 160 KB per workgroup once the attribute is raised
             MMPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          static_cast<int>(lds)));
@@ -1388,12 +1417,14 @@ int launch_gain_kernels(int kernel, const GainParams& p, size_t lds, hipStream_t
 }
 // a gain call whose arguments check_gain_args has passed, B > 0, device pointers, on the current device: one launch,
 // stream-ordered, no allocation, no synchronisation
-int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact) {
+int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact, const XbTail& xb) {
     const mmpc_model_info& mi = h->info;
     if (a.kernel == MMPC_GAIN_KERNEL_AUTO)
         if (int rc = query_cu_count(h)) return rc;
-    const int kernel = resolve_gain_kernel(h, a.B, exact, a.kernel);
-    GainParams p{};
+    const bool xbv = xb.mu > 0.0;
+    const int kernel = resolve_gain_kernel(h, a.B, exact, xbv, a.kernel);
+    GainXbParams p{};
+    p.xb = xb;
     p.B = a.B;
     p.N = mi.num_shooting_nodes;
     p.h = mi.step_size;
@@ -1409,19 +1440,21 @@ int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact) {
     p.n_gain = a.n_gain;
     p.G = a.G;
     p.status = a.status;
-    p.gpw = kernel == MMPC_GAIN_KERNEL_GROUP ? gain_group_gpw(mi, exact) : 1;
+    p.gpw = kernel == MMPC_GAIN_KERNEL_GROUP ? gain_group_gpw(mi, exact, xbv) : 1;
     const size_t lds = kernel == MMPC_GAIN_KERNEL_GROUP
-                           ? static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, p.N, exact)) * p.gpw *
+                           ? static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, p.N, exact, xbv)) * p.gpw *
                                  sizeof(double)
                            : 0;
     const bool bounded = a.u_lb || a.u_ub;
     return with_model(mi.model_id, [&](auto* m) {
         using M = std::remove_pointer_t<decltype(m)>;
         if constexpr (HasHess<M>::value) {
+            if (exact && xbv) return launch_gain_kernels<M, true, true, true>(kernel, p, lds, a.stream);
             if (exact)
                 return bounded ? launch_gain_kernels<M, true, true>(kernel, p, lds, a.stream)
                                : launch_gain_kernels<M, true, false>(kernel, p, lds, a.stream);
         }
+        if (xbv) return launch_gain_kernels<M, false, true, true>(kernel, p, lds, a.stream);
         return bounded ? launch_gain_kernels<M, false, true>(kernel, p, lds, a.stream)
                        : launch_gain_kernels<M, false, false>(kernel, p, lds, a.stream);
     });
@@ -1452,7 +1485,7 @@ uint64_t vjp_workspace_bytes(const mmpc_model_info& mi, int64_t B) {
 }
 // The one check of a VJP call's arguments: pure arithmetic on the arguments and the handle, before any device call
 // (check_gain_args's rules; the host entry brings its own workspace and passes check_workspace = false).
-int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool* exact) {
+int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool* exact, XbTail* xb) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     const mmpc_model_info& mi = h->info;
     const int N = mi.num_shooting_nodes;
@@ -1464,12 +1497,7 @@ int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool*
     if (a.hessian < MMPC_HESSIAN_AUTO || a.hessian > MMPC_HESSIAN_EXACT)
         return fail(MMPC_ERR_INVALID_ARG, "hessian: not an mmpc_hessian value (" + std::to_string(a.hessian) + ")");
     if (mi.is_linear) return fail(MMPC_ERR_UNSUPPORTED, "the solve VJP is not available for a linear-mode model");
-    {
-        std::lock_guard<std::mutex> lk(h->xb_mu);
-        if (h->x_bounded)
-            return fail(MMPC_ERR_UNSUPPORTED, "the solve VJP is not available with finite state bounds "
-                                              "(barrier-smoothed sensitivities are not computed)");
-    }
+    if (int rc = read_sens_barrier(h, "the solve VJP is", xb)) return rc;
     bool has_hess = false;
     with_model(mi.model_id, [&](auto* m) {
         has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
@@ -1497,9 +1525,10 @@ int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool*
 }
 // a VJP call whose arguments check_vjp_args has passed, B > 0, device pointers, on the current device: one launch,
 // stream-ordered, no allocation, no synchronisation
-int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact) {
+int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact, const XbTail& xb) {
     const mmpc_model_info& mi = h->info;
-    AdjointParams p{};
+    AdjointXbParams p{};
+    p.xb = xb;
     p.B = a.B;
     p.N = mi.num_shooting_nodes;
     p.h = mi.step_size;
@@ -1529,10 +1558,12 @@ int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact) {
     return with_model(mi.model_id, [&](auto* m) {
         using M = std::remove_pointer_t<decltype(m)>;
         if constexpr (HasHess<M>::value) {
+            if (exact && xb.mu > 0.0) return launch(&adjoint_lane_kernel<M, true, true, true>);
             if (exact)
                 return bounded ? launch(&adjoint_lane_kernel<M, true, true>)
                                : launch(&adjoint_lane_kernel<M, true, false>);
         }
+        if (xb.mu > 0.0) return launch(&adjoint_lane_kernel<M, false, true, true>);
         return bounded ? launch(&adjoint_lane_kernel<M, false, true>) : launch(&adjoint_lane_kernel<M, false, false>);
     });
 }
@@ -1679,6 +1710,33 @@ int mmpc_set_barrier_rule(mmpc_handle* h, int32_t rule) {
 int mmpc_get_barrier_rule(const mmpc_handle* h, int32_t* rule) {
     if (!h || !rule) return fail(MMPC_ERR_INVALID_ARG, "null argument");
     *rule = h->barrier_rule;
+    return MMPC_OK;
+}
+
+int mmpc_sensitivity_barrier_default(double* mu, double* sigma_cap) {
+    if (!mu || !sigma_cap) return fail(MMPC_ERR_INVALID_ARG, "null argument");
+    *mu = sens_mu_default();
+    *sigma_cap = kSensCapDefault;
+    return MMPC_OK;
+}
+
+int mmpc_set_sensitivity_barrier(mmpc_handle* h, double mu, double sigma_cap) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (!(mu >= 0.0) || !std::isfinite(mu))
+        return fail(MMPC_ERR_INVALID_ARG, "mu must be finite and >= 0 (0 switches the barrier off), got " +
+                                              std::to_string(mu));
+    if (!(sigma_cap > 0.0))
+        return fail(MMPC_ERR_INVALID_ARG, "sigma_cap must be > 0 (+inf: no cap), got " + std::to_string(sigma_cap));
+    std::lock_guard<std::mutex> lk(h->xb_mu);
+    h->sens_mu = mu;
+    h->sens_cap = sigma_cap;
+    return MMPC_OK;
+}
+
+int mmpc_get_sensitivity_barrier(const mmpc_handle* h, double* mu, double* sigma_cap) {
+    if (!h || !mu || !sigma_cap) return fail(MMPC_ERR_INVALID_ARG, "null argument");
+    *mu = h->sens_mu;
+    *sigma_cap = h->sens_cap;
     return MMPC_OK;
 }
 
@@ -1844,14 +1902,15 @@ int mmpc_feedback_gains_batch(mmpc_handle* h, int64_t B, const double* V, const 
     const GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian,
                      kernel, G_out, gain_status, reinterpret_cast<hipStream_t>(stream)};
     bool exact = false;
-    if (int rc = check_gain_args(h, a, &exact)) return rc;
+    XbTail xb;
+    if (int rc = check_gain_args(h, a, &exact, &xb)) return rc;
     if (B == 0) return MMPC_OK;
     int dev;
     int rc = resolve_device(h, &dev);
     if (rc) return rc;
     DeviceGuard g(dev);
     if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_gains(h, a, exact);
+    return launch_gains(h, a, exact, xb);
 }
 
 int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev,
@@ -1862,7 +1921,8 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
     GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian, kernel,
                G_out, gain_status};
     bool exact = false;
-    if (int rc = check_gain_args(h, a, &exact)) return rc;   // before weights_stride and bounds_stride size a copy
+    XbTail xb;
+    if (int rc = check_gain_args(h, a, &exact, &xb)) return rc;   // before weights_stride and bounds_stride size a copy
     if (B == 0) return MMPC_OK;
     std::lock_guard<std::mutex> lk(h->host_mu);
     const mmpc_model_info& mi = h->info;
@@ -1899,7 +1959,7 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
     a.G = d + off_G;
     a.status = dst;
     a.stream = s;
-    if ((rc = launch_gains(h, a, exact))) return rc;
+    if ((rc = launch_gains(h, a, exact, xb))) return rc;
     MMPC_HIP(hipMemcpyAsync(G_out, d + off_G, nG * sizeof(double), hipMemcpyDeviceToHost, s));
     if (gain_status) MMPC_HIP(hipMemcpyAsync(gain_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MMPC_HIP(hipStreamSynchronize(s));
@@ -1921,14 +1981,15 @@ int mmpc_solve_vjp_batch(mmpc_handle* h, int64_t B, const double* V, const doubl
                     x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status, workspace, workspace_bytes,
                     reinterpret_cast<hipStream_t>(stream)};
     bool exact = false;
-    if (int rc = check_vjp_args(h, a, true, &exact)) return rc;
+    XbTail xb;
+    if (int rc = check_vjp_args(h, a, true, &exact, &xb)) return rc;
     if (B == 0) return MMPC_OK;
     int dev;
     int rc = resolve_device(h, &dev);
     if (rc) return rc;
     DeviceGuard g(dev);
     if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_vjp(h, a, exact);
+    return launch_vjp(h, a, exact, xb);
 }
 
 int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
@@ -1939,7 +2000,8 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
     VjpArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, V_bar, hessian,
               x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status};
     bool exact = false;
-    if (int rc = check_vjp_args(h, a, false, &exact)) return rc;   // before the strides size a copy
+    XbTail xb;
+    if (int rc = check_vjp_args(h, a, false, &exact, &xb)) return rc;   // before the strides size a copy
     if (B == 0) return MMPC_OK;
     std::lock_guard<std::mutex> lk(h->host_mu);
     const mmpc_model_info& mi = h->info;
@@ -1986,7 +2048,7 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
     a.workspace = nWs ? d + off_ws : nullptr;
     a.workspace_bytes = nWs * sizeof(double);
     a.stream = s;
-    if ((rc = launch_vjp(h, a, exact))) return rc;
+    if ((rc = launch_vjp(h, a, exact, xb))) return rc;
     const auto back = [&](double* dst_host, size_t off, size_t n) {
         return dst_host ? hipMemcpyAsync(dst_host, d + off, n * sizeof(double), hipMemcpyDeviceToHost, s) : hipSuccess;
     };

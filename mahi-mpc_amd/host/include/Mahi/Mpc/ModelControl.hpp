@@ -62,6 +62,12 @@ public:
     // (default), 1 = Mehrotra's predictor-corrector (mmpc_set_barrier_rule in include/mmpc.h: 16-lane solver, nonlinear
     // mode; a solve it does not cover then throws).  Additive: not part of the reference's interface.
     void set_barrier_rule(int rule);
+    // Feedback under state limits.  set_feedback_stages on a controller whose JSON or setters carry state limits needs
+    // the sensitivity barrier switched on (mmpc_set_sensitivity_barrier in include/mmpc.h): the gains are then those of
+    // the interior point's barrier problem at the plan.  mu < 0: the library's default (the barrier value a
+    // monotone-rule solve ends at), mu = 0: off (the state of a new object); sigma_cap <= 0: the library's default
+    // (1e12).  Without state limits the setting has no effect.
+    void set_sensitivity_barrier(double mu = -1.0, double sigma_cap = 0.0);
     // Committed controls (delay compensation): the setter the reference's private m_num_control_inputs_saved
     // (ModelControl.hpp:79) never got.  From the second calc_u on, the first m controls of the horizon are pinned to the
     // controls the previous plan holds for those instants: stage i < m gets the previous plan's control at index

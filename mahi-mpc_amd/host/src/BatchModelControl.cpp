@@ -542,6 +542,14 @@ void BatchModelControl::set_num_control_inputs_saved(int m_pin) {
     m_num_control_inputs_saved = m_pin;
 }
 
+void BatchModelControl::set_sensitivity_barrier(double mu, double sigma_cap) {
+    std::lock_guard<std::mutex> lg(m_solve_mutex);   // between ticks
+    double dmu = 0.0, dcap = 0.0;
+    m->check(m->lib->sensitivity_barrier_default(&dmu, &dcap), "mmpc_sensitivity_barrier_default");
+    m->check(m->lib->set_sensitivity_barrier(m->h, mu < 0.0 ? dmu : mu, sigma_cap > 0.0 ? sigma_cap : dcap),
+             "mmpc_set_sensitivity_barrier");
+}
+
 void BatchModelControl::set_barrier_rule(int rule) {
     std::lock_guard<std::mutex> lg(m_solve_mutex);   // between ticks
     m->check(m->lib->set_barrier_rule(m->h, rule), "mmpc_set_barrier_rule");

@@ -325,6 +325,14 @@ void ModelControl::set_num_control_inputs_saved(int m) {
     m_num_control_inputs_saved = m;
 }
 
+void ModelControl::set_sensitivity_barrier(double mu, double sigma_cap) {
+    double dmu = 0.0, dcap = 0.0;
+    m_backend->check(m_backend->sensitivity_barrier_default(&dmu, &dcap), "mmpc_sensitivity_barrier_default");
+    m_backend->check(
+        m_backend->set_sensitivity_barrier(m_handle, mu < 0.0 ? dmu : mu, sigma_cap > 0.0 ? sigma_cap : dcap),
+        "mmpc_set_sensitivity_barrier");
+}
+
 void ModelControl::set_barrier_rule(int rule) {
     m_backend->check(m_backend->set_barrier_rule(m_handle, rule), "mmpc_set_barrier_rule");
 }

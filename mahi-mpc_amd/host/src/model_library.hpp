@@ -37,6 +37,9 @@ struct ModelLibrary {
     decltype(&mmpc_feedback_gains_batch_host) feedback_gains_batch_host = &mmpc_feedback_gains_batch_host;
     decltype(&mmpc_reserve_workspace) reserve_workspace = &mmpc_reserve_workspace;
     decltype(&mmpc_set_barrier_rule) set_barrier_rule = &mmpc_set_barrier_rule;
+    // feedback under state limits: the mirror of set_sensitivity_barrier
+    decltype(&mmpc_sensitivity_barrier_default) sensitivity_barrier_default = &mmpc_sensitivity_barrier_default;
+    decltype(&mmpc_set_sensitivity_barrier) set_sensitivity_barrier = &mmpc_set_sensitivity_barrier;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
     void* dl = nullptr;  // kept loaded for the process lifetime (HIP code objects), as CasADi keeps its libraries
 
@@ -88,6 +91,8 @@ struct ModelLibrary {
         b->bind(b->feedback_gains_batch_host, "mmpc_feedback_gains_batch_host");
         b->bind(b->reserve_workspace, "mmpc_reserve_workspace");
         b->bind(b->set_barrier_rule, "mmpc_set_barrier_rule");
+        b->bind(b->sensitivity_barrier_default, "mmpc_sensitivity_barrier_default");
+        b->bind(b->set_sensitivity_barrier, "mmpc_set_sensitivity_barrier");
         b->bind(b->last_error, "mmpc_last_error");
         return b;
     }

@@ -159,6 +159,10 @@ def lib(path: str | None = None):
         L.mmpc_get_state_bounds.argtypes = [_vp, _vp, _vp]
         L.mmpc_set_barrier_rule.argtypes = [_vp, C.c_int32]
         L.mmpc_get_barrier_rule.argtypes = [_vp, C.POINTER(C.c_int32)]
+        _pd = C.POINTER(C.c_double)
+        L.mmpc_sensitivity_barrier_default.argtypes = [_pd, _pd]
+        L.mmpc_set_sensitivity_barrier.argtypes = [_vp, C.c_double, C.c_double]
+        L.mmpc_get_sensitivity_barrier.argtypes = [_vp, _pd, _pd]
         L.mmpc_status_string.argtypes = [C.c_int32]
         L.mmpc_status_string.restype = C.c_char_p
         L.mmpc_last_error.restype = C.c_char_p
@@ -311,7 +315,7 @@ class Solver:
 
     def __init__(self, model_json=None, json_text=None, max_iter=None, tol_grad=None, tol_defect=None,
                  device=None, kkt_solver=None, factor_fp32=None, library=None, init_states=None, hessian=None,
-                 tail_cap=None, tail_wave_max=None, tail_rounds=None, barrier_rule=None):
+                 tail_cap=None, tail_wave_max=None, tail_rounds=None, barrier_rule=None, sensitivity_barrier=None):
         self._L = L = lib(library or (model_library(model_json) if model_json is not None else None))
         o = Opts()
         L.mmpc_default_opts(C.byref(o))
@@ -351,6 +355,15 @@ class Solver:
         self.h = info.step_size
         if barrier_rule is not None:
             self.set_barrier_rule(barrier_rule)
+        if sensitivity_barrier is not None:   # True: the library's defaults; a number: mu; a pair: (mu, sigma_cap)
+            if sensitivity_barrier is True:
+                self.set_sensitivity_barrier()
+            elif sensitivity_barrier is False:
+                self.set_sensitivity_barrier(mu=0)
+            elif np.ndim(sensitivity_barrier) == 0:
+                self.set_sensitivity_barrier(mu=sensitivity_barrier)
+            else:
+                self.set_sensitivity_barrier(*sensitivity_barrier)
 
     def _check(self, rc):
         _check(rc, self._L)
@@ -572,6 +585,22 @@ class Solver:
         r = C.c_int32(-1)
         self._check(self._L.mmpc_get_barrier_rule(self._h, C.byref(r)))
         return int(r.value)
+
+    def set_sensitivity_barrier(self, mu=None, sigma_cap=None):
+        """Barrier of the feedback gains and the solve VJP on a state-bounded solver (mmpc_set_sensitivity_barrier):
+        None is the library's default (the barrier value a monotone-rule solve ends at, cap 1e12), mu=0 switches it
+        off -- the state of a new solver, in which those calls refuse a state-bounded solver."""
+        dm, dc = C.c_double(), C.c_double()
+        self._check(self._L.mmpc_sensitivity_barrier_default(C.byref(dm), C.byref(dc)))
+        self._check(self._L.mmpc_set_sensitivity_barrier(self._h, dm.value if mu is None else float(mu),
+                                                         dc.value if sigma_cap is None else float(sigma_cap)))
+
+    @property
+    def sensitivity_barrier(self):
+        """(mu, sigma_cap) of set_sensitivity_barrier; mu = 0: off"""
+        mu, cap = C.c_double(), C.c_double()
+        self._check(self._L.mmpc_get_sensitivity_barrier(self._h, C.byref(mu), C.byref(cap)))
+        return mu.value, cap.value
 
     def kkt_solver_for(self, B: int) -> int:
         """KKT_* solver a solve of B instances runs (the AUTO choice resolved)."""

@@ -3,7 +3,10 @@
 ``DifferentiableSolver(solver)`` wraps a ``mmpc.Solver``: calling it runs ``Solver.solve_batch`` on the current torch
 stream, and ``.backward()`` through the returned V* runs one ``Solver.solve_vjp`` launch at the saved solution -- the
 gradients with respect to x0, u_prev, traj and the weights for about the cost of one SQP iteration.  Control bounds
-and the warm start get no gradient.  This module imports torch; ``import mmpc`` does not import it.
+and the warm start get no gradient.  A solver with finite state bounds needs its sensitivity barrier switched on
+(``Solver.set_sensitivity_barrier()``): the backward pass then runs the barrier recursion with the
+control bounds it saved, and raises MmpcError -4 otherwise.  This module imports torch; ``import mmpc`` does not import
+it.
 """
 from __future__ import annotations
 
