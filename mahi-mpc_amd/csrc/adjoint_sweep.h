@@ -13,25 +13,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "gain_sweep.h"
 
 namespace mmpc {
 
-struct AdjointParams {
-    int64_t B;
-    int N;
-    double h;
-    const double* V;        // [B][NV]
-    const double* u_prev;   // [B][nu]
-    const double* traj;     // [B][N][nx]
-    const double* weights;  // (Q | R | Rm), row b at b * w_stride
-    int64_t w_stride;
-    const double* u_lb;     // BOUNDED kernels: [nu] (b_stride 0) or row b at b * b_stride; either may be null
-    const double* u_ub;
-    int32_t b_stride;
-    int32_t n_pin;          // stages k < n_pin are held (committed controls)
+struct AdjointParams : SensParams {   // the head: gain_sweep.h
     const double* V_bar;    // [B][NV]
     double* x0_bar;         // [B][nx] or null
     double* u_prev_bar;     // [B][nu] or null
@@ -41,6 +30,10 @@ struct AdjointParams {
     int32_t* status;        // [B] or null: 0 as asked, 1 Gauss-Newton fallback, 2 failed (every output row 0)
     double* ws;             // the records; null in backward-only mode (traj_bar, weights_bar and adj_V all null)
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(AdjointParams) == 152 && offsetof(AdjointParams, V_bar) == 88, "kernel argument layout");
+#pragma clang diagnostic pop
 
 // workspace doubles per lane: the record G_k | kff_k of every stage
 __host__ __device__ constexpr int64_t adjoint_rec_doubles(int nx, int nu) { return (int64_t)nu * (nx + nu + 1); }
@@ -49,21 +42,22 @@ __host__ __device__ constexpr int64_t adjoint_lane_doubles(int nx, int nu, int N
 }
 
 // the XB instantiations' parameters: AdjointParams plus the sensitivity barrier's tail (gain_sweep.h); AdjointParams
-// itself, and with it the other instantiations' kernel arguments, stays as it is
+// itself, and with it the other instantiations' kernel arguments, keeps its layout
 struct AdjointXbParams : AdjointParams {
     XbTail xb;
 };
 template <bool XB>
 using AdjointParamsOf = std::conditional_t<XB, AdjointXbParams, AdjointParams>;
 
-// One lane per instance, both sweeps in one launch.  The backward sweep is gain_lane_kernel's fused stage (restated
-// here, that kernel is left as it is) plus q, kff and p; with a workspace it stores G_k | kff_k per stage, element i of
+// One lane per instance, both sweeps in one launch.  The backward sweep is gain_lane_kernel's fused stage -- one text
+// for both kernels, sens_lane_stage.inc: part 1 through G_k, then q, kff and p here, then part 2 (P_k) -- and the
+// prologue is that file's part 0; with a workspace it stores G_k | kff_k per stage, element i of
 // lane l of workgroup g at ws[(g * doubles per lane + i) * 64 + l], so a wave's store of one element is one 512-byte
 // line.  The forward sweep evaluates value and Jacobian again per stage (nothing of [A | B] is stored), reads the
 // record back, writes adj_V and traj_bar per stage and keeps the nx + 2 nu weight sums in registers.  A second pass
 // over both sweeps runs only for the Gauss-Newton fallback.  XB: the sensitivity barrier's terms join the backward
-// stage as in gain_lane_kernel (XbTail, gain_sweep.h); q, kff, p, the forward sweep and the outputs are the same text,
-// the barrier does not depend on theta.
+// stage inside the shared text (XbTail, gain_sweep.h); q, kff, p, the forward sweep and the outputs are the same text
+// with and without XB, the barrier does not depend on theta.
 template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
 __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParamsOf<XB> p) {
     constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU, NQ = Model::NQ, NA = NX - NQ, NP = K * (K + 1) / 2;
@@ -83,23 +77,8 @@ __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParamsOf<
     double* const rec = full ? p.ws + (int64_t)blockIdx.x * ((int64_t)N * RD * 64) + threadIdx.x : nullptr;
     double* const trb = p.traj_bar ? p.traj_bar + b * (int64_t)N * NX : nullptr;
     double* const av = p.adj_V ? p.adj_V + b * NV : nullptr;
-    double Q[NX], R[NU], Rm[NU], lb[NU], ub[NU], up[NU];
-    // inputs the backward sweep never multiplies into a pivot: x_N, u_prev
-    double fin = 0.0;
-#pragma unroll
-    for (int r = 0; r < NX; ++r) {
-        Q[r] = w[r];
-        fin += gain_nonfinite(v[(int64_t)N * K + r]) + gain_nonfinite(Q[r]);
-    }
-#pragma unroll
-    for (int c = 0; c < NU; ++c) {
-        R[c] = w[NX + c];
-        Rm[c] = w[NX + NU + c];
-        up[c] = p.u_prev[b * NU + c];
-        fin += gain_nonfinite(up[c]) + gain_nonfinite(R[c]) + gain_nonfinite(Rm[c]);
-        lb[c] = (BOUNDED && p.u_lb) ? p.u_lb[b * p.b_stride + c] : -INFINITY;
-        ub[c] = (BOUNDED && p.u_ub) ? p.u_ub[b * p.b_stride + c] : INFINITY;
-    }
+#define MMPC_SENS_PART 0   // Q, R, Rm, lb, ub, up, fin
+#include "sens_lane_stage.inc"
     bool ok = false;
     int st = 0;
     double pv[K], wb[NX + 2 * NU];   // p_k; the weight sums (Q_bar | R_bar | Rm_bar)
@@ -121,110 +100,8 @@ __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParamsOf<
 #pragma unroll
         for (int c = 0; c < NU; ++c) pv[NX + c] = 0.0;
         for (int k = N - 1; k >= 0 && ok; --k) {
-            double x[NX], u[NU], xd[NX], fx[NX * NX], fu[NX * NU];
-#pragma unroll
-            for (int r = 0; r < NX; ++r) x[r] = v[k * K + r];
-#pragma unroll
-            for (int c = 0; c < NU; ++c) u[c] = v[k * K + NX + c];
-            model_eval_jac<Model>(x, u, xd, fx, fu);
-            double J[NX][K], nuk[NX], chk = 0.0;   // J = [A_k | B_k]
-            [[maybe_unused]] double Du[NU];
-            if constexpr (XB) {   // lam_k gets beta(x_{k+1}), P_{k+1} gets D(x_{k+1}) in place; D(u_k) for M_uu
-                bool in = true;
-#pragma unroll
-                for (int r = 0; r < NX; ++r) {
-                    double be, D;
-                    in = xb_terms(v[(k + 1) * K + r], p.xb.x_lb[r], p.xb.x_ub[r], p.xb.mu, p.xb.cap, be, D) && in;
-                    lam[r] += be;
-                    P[gain_sym(r, r, K)] += D;
-                }
-#pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    double be;
-                    Du[c] = 0.0;
-                    if (k >= p.n_pin) in = xb_terms(u[c], lb[c], ub[c], p.xb.mu, p.xb.cap, be, Du[c]) && in;
-                }
-                chk += in ? 0.0 : NAN;
-            }
-#pragma unroll
-            for (int r = 0; r < NX; ++r) {
-#pragma unroll
-                for (int c = 0; c < NX; ++c) J[r][c] = (r == c ? 1.0 : 0.0) + h * fx[r * NX + c];
-#pragma unroll
-                for (int c = 0; c < NU; ++c) J[r][NX + c] = h * fu[r * NU + c];
-                const double e = x[r] + h * xd[r] - tr[k * NX + r];
-                nuk[r] = 2.0 * Q[r] * e + lam[r];
-                chk += gain_nonfinite(nuk[r]);   // a non-finite target fails the instance under either Hessian
-            }
-#pragma unroll
-            for (int c = 0; c < NX; ++c) {   // lam_{k-1} = A_k^T nu_k
-                double s = 0.0;
-#pragma unroll
-                for (int r = 0; r < NX; ++r) s += J[r][c] * nuk[r];
-                lam[c] = s;
-            }
-            // M_yy = C^T P C + S_k, column by column of P C
-            double M[NP];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                double t[K];
-#pragma unroll
-                for (int a = 0; a < K; ++a) {
-                    double s = j >= NX ? P[gain_sym(a, j, K)] : 0.0;
-#pragma unroll
-                    for (int q = 0; q < NX; ++q) s += P[gain_sym(a, q, K)] * J[q][j];
-                    t[a] = s;
-                }
-#pragma unroll
-                for (int i = 0; i <= j; ++i) {
-                    double s = i >= NX ? t[i] : 0.0;
-#pragma unroll
-                    for (int a = 0; a < NX; ++a) s += J[a][i] * t[a];
-#pragma unroll
-                    for (int r = 0; r < NX; ++r) s += 2.0 * Q[r] * J[r][i] * J[r][j];
-                    M[gain_sym(i, j, K)] = s;
-                }
-            }
-            if constexpr (EXACT) {
-                if (exact) {
-                    double la[NA], W[K * K];
-#pragma unroll
-                    for (int s2 = 0; s2 < NA; ++s2) la[s2] = h * nuk[NQ + s2];
-                    Model::eval_hess(x, u, la, W);
-#pragma unroll
-                    for (int i = 0; i < K; ++i)
-#pragma unroll
-                        for (int j = i; j < K; ++j) M[gain_sym(i, j, K)] += W[i * K + j];
-                }
-            }
-            double Muu[NU][NU], Mus[NU][K], il[NU];
-            bool held[NU];
-#pragma unroll
-            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED && !XB>(k, p.n_pin, u[c], lb[c], ub[c]);
-#pragma unroll
-            for (int c = 0; c < NU; ++c) {
-#pragma unroll
-                for (int d = 0; d < NU; ++d) {
-                    double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
-                    if constexpr (XB) m += c == d ? Du[c] : 0.0;
-                    Muu[c][d] = (held[c] || held[d]) ? (c == d ? 1.0 : 0.0) : m;
-                }
-#pragma unroll
-                for (int j = 0; j < NX; ++j) Mus[c][j] = held[c] ? 0.0 : M[gain_sym(j, NX + c, K)];
-#pragma unroll
-                for (int d = 0; d < NU; ++d) Mus[c][NX + d] = (c == d && !held[c]) ? -2.0 * R[c] : 0.0;
-            }
-            ok = gain_chol<NU>(Muu, il);
-            double G[NU][K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                double m[NU], g[NU];
-#pragma unroll
-                for (int c = 0; c < NU; ++c) m[c] = Mus[c][j];
-                gain_solve<NU>(Muu, il, m, g);
-#pragma unroll
-                for (int c = 0; c < NU; ++c) G[c][j] = held[c] ? 0.0 : g[c];
-            }
+#define MMPC_SENS_PART 1   // the model, nu_k / lam, M_yy (+ W_k), the held rows, the factor of M_uu, G_k
+#include "sens_lane_stage.inc"
             // q = C_k^T p_{k+1} + V_bar_{y_k}; kff_k = M_uu^-1 q_u; p_k = (q_x; 0) + G_k^T q_u
             double q[K], mq[NU], kff[NU];
 #pragma unroll
@@ -253,17 +130,8 @@ __global__ __launch_bounds__(64) void adjoint_lane_kernel(const AdjointParamsOf<
                 pv[j] = s;
                 chk += gain_nonfinite(s);
             }
-            // P_k = M_ss + M_su G_k
-#pragma unroll
-            for (int i = 0; i < K; ++i)
-#pragma unroll
-                for (int j = i; j < K; ++j) {
-                    double s = (j < NX) ? M[gain_sym(i, j, K)] : ((i == j) ? 2.0 * R[i - (i >= NX ? NX : 0)] : 0.0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) s += Mus[c][i] * G[c][j];
-                    P[gain_sym(i, j, K)] = s;
-                    chk += gain_nonfinite(s);
-                }
+#define MMPC_SENS_PART 2   // P_k = M_ss + M_su G_k
+#include "sens_lane_stage.inc"
             ok = ok && chk == 0.0;
             if (ok && full) {
                 double* const rk = rec + (int64_t)k * (RD * 64);

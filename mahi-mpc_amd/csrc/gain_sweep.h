@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 
@@ -26,7 +27,9 @@
 
 namespace mmpc {
 
-struct GainParams {
+// The head of every sensitivity kernel's parameters (the gain kernels here, the adjoint kernel of adjoint_sweep.h): the
+// plan and the problem it solved.  The shared kernel text (sens_lane_stage.inc) reads only these and, with XB, the tail.
+struct SensParams {
     int64_t B;
     int N;
     double h;
@@ -39,11 +42,20 @@ struct GainParams {
     const double* u_ub;
     int32_t b_stride;
     int32_t n_pin;          // stages k < n_pin are held (committed controls)
+};
+struct GainParams : SensParams {
     int32_t n_gain;         // stages written
     double* G;              // [B][n_gain][nu][nx + nu]
     int32_t* status;        // [B] or null: 0 as asked, 1 Gauss-Newton fallback, 2 failed (gains 0)
     int gpw;                // 16-lane kernel: instances per workgroup (<= kGroupsPerWave)
 };
+// the kernel arguments' layout is the one the structs had with the head written out member by member (offsetof of a
+// struct with a base is conditionally supported; the compiler of HIP supports it and says so with a warning)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(SensParams) == 88 && sizeof(GainParams) == 120, "kernel argument layout");
+static_assert(offsetof(GainParams, n_gain) == 88, "kernel argument layout");
+#pragma clang diagnostic pop
 
 // The sensitivity barrier of a state-bounded handle (mmpc_set_sensitivity_barrier, include/mmpc.h): the
 // XB instantiations take GainParams plus this tail, so the kernel arguments of every other instantiation stay as
@@ -142,7 +154,8 @@ __device__ __forceinline__ bool gain_held(int k, int n_pin, double u, double lb,
 
 // One lane per instance: a single fused backward sweep -- Jacobian, nu / lam, W_k, the stage step and the store of
 // G_k for k < n_gain per stage.  No workspace: the only traffic is V, the targets and G.  A second pass runs only
-// for the Gauss-Newton fallback.  XB: the sensitivity barrier's terms join the stage (XbTail).
+// for the Gauss-Newton fallback.  XB: the sensitivity barrier's terms join the stage (XbTail).  The prologue and the
+// stage are the text of sens_lane_stage.inc, which adjoint_lane_kernel (adjoint_sweep.h) compiles in too: parts 0, 1, 2.
 template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
 __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParamsOf<XB> p) {
     constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU, NQ = Model::NQ, NA = NX - NQ, NP = K * (K + 1) / 2;
@@ -157,22 +170,8 @@ __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParamsOf<XB> p)
     const double* w = p.weights + b * p.w_stride;
     const double* tr = p.traj + b * (int64_t)N * NX;
     double* Gb = p.G + b * (int64_t)p.n_gain * (NU * K);
-    double Q[NX], R[NU], Rm[NU], lb[NU], ub[NU];
-    // inputs the sweep itself never multiplies into a pivot: x_N, u_prev (the gains do not depend on them)
-    double fin = 0.0;
-#pragma unroll
-    for (int r = 0; r < NX; ++r) {
-        Q[r] = w[r];
-        fin += gain_nonfinite(v[(int64_t)N * K + r]) + gain_nonfinite(Q[r]);
-    }
-#pragma unroll
-    for (int c = 0; c < NU; ++c) {
-        R[c] = w[NX + c];
-        Rm[c] = w[NX + NU + c];
-        fin += gain_nonfinite(p.u_prev[b * NU + c]) + gain_nonfinite(R[c]) + gain_nonfinite(Rm[c]);
-        lb[c] = (BOUNDED && p.u_lb) ? p.u_lb[b * p.b_stride + c] : -INFINITY;
-        ub[c] = (BOUNDED && p.u_ub) ? p.u_ub[b * p.b_stride + c] : INFINITY;
-    }
+#define MMPC_SENS_PART 0   // Q, R, Rm, lb, ub, up, fin
+#include "sens_lane_stage.inc"
     bool ok = false;
     int st = 0;
     for (int pass = 0; pass < (EXACT ? 2 : 1) && !ok; ++pass) {
@@ -185,121 +184,10 @@ __global__ __launch_bounds__(64) void gain_lane_kernel(const GainParamsOf<XB> p)
 #pragma unroll
         for (int r = 0; r < NX; ++r) lam[r] = 0.0;
         for (int k = N - 1; k >= 0 && ok; --k) {
-            double x[NX], u[NU], xd[NX], fx[NX * NX], fu[NX * NU];
-#pragma unroll
-            for (int r = 0; r < NX; ++r) x[r] = v[k * K + r];
-#pragma unroll
-            for (int c = 0; c < NU; ++c) u[c] = v[k * K + NX + c];
-            model_eval_jac<Model>(x, u, xd, fx, fu);
-            double J[NX][K], nuk[NX], chk = 0.0;   // J = [A_k | B_k]
-            [[maybe_unused]] double Du[NU];
-            if constexpr (XB) {   // lam_k gets beta(x_{k+1}), P_{k+1} gets D(x_{k+1}) in place; D(u_k) for M_uu
-                bool in = true;
-#pragma unroll
-                for (int r = 0; r < NX; ++r) {
-                    double be, D;
-                    in = xb_terms(v[(k + 1) * K + r], p.xb.x_lb[r], p.xb.x_ub[r], p.xb.mu, p.xb.cap, be, D) && in;
-                    lam[r] += be;
-                    P[gain_sym(r, r, K)] += D;
-                }
-#pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    double be;
-                    Du[c] = 0.0;
-                    if (k >= p.n_pin) in = xb_terms(u[c], lb[c], ub[c], p.xb.mu, p.xb.cap, be, Du[c]) && in;
-                }
-                chk += in ? 0.0 : NAN;
-            }
-#pragma unroll
-            for (int r = 0; r < NX; ++r) {
-#pragma unroll
-                for (int c = 0; c < NX; ++c) J[r][c] = (r == c ? 1.0 : 0.0) + h * fx[r * NX + c];
-#pragma unroll
-                for (int c = 0; c < NU; ++c) J[r][NX + c] = h * fu[r * NU + c];
-                const double e = x[r] + h * xd[r] - tr[k * NX + r];
-                nuk[r] = 2.0 * Q[r] * e + lam[r];
-                chk += gain_nonfinite(nuk[r]);   // a non-finite target fails the instance under either Hessian
-            }
-#pragma unroll
-            for (int c = 0; c < NX; ++c) {   // lam_{k-1} = A_k^T nu_k
-                double s = 0.0;
-#pragma unroll
-                for (int r = 0; r < NX; ++r) s += J[r][c] * nuk[r];
-                lam[c] = s;
-            }
-            // M_yy = C^T P C + S_k, column by column of P C
-            double M[NP];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                double t[K];
-#pragma unroll
-                for (int a = 0; a < K; ++a) {
-                    double s = j >= NX ? P[gain_sym(a, j, K)] : 0.0;
-#pragma unroll
-                    for (int q = 0; q < NX; ++q) s += P[gain_sym(a, q, K)] * J[q][j];
-                    t[a] = s;
-                }
-#pragma unroll
-                for (int i = 0; i <= j; ++i) {
-                    double s = i >= NX ? t[i] : 0.0;
-#pragma unroll
-                    for (int a = 0; a < NX; ++a) s += J[a][i] * t[a];
-#pragma unroll
-                    for (int r = 0; r < NX; ++r) s += 2.0 * Q[r] * J[r][i] * J[r][j];
-                    M[gain_sym(i, j, K)] = s;
-                }
-            }
-            if constexpr (EXACT) {
-                if (exact) {
-                    double la[NA], W[K * K];
-#pragma unroll
-                    for (int s2 = 0; s2 < NA; ++s2) la[s2] = h * nuk[NQ + s2];
-                    Model::eval_hess(x, u, la, W);
-#pragma unroll
-                    for (int i = 0; i < K; ++i)
-#pragma unroll
-                        for (int j = i; j < K; ++j) M[gain_sym(i, j, K)] += W[i * K + j];
-                }
-            }
-            double Muu[NU][NU], Mus[NU][K], il[NU];
-            bool held[NU];
-#pragma unroll
-            for (int c = 0; c < NU; ++c) held[c] = gain_held<BOUNDED && !XB>(k, p.n_pin, u[c], lb[c], ub[c]);
-#pragma unroll
-            for (int c = 0; c < NU; ++c) {
-#pragma unroll
-                for (int d = 0; d < NU; ++d) {
-                    double m = M[gain_sym(NX + c, NX + d, K)] + (c == d ? 2.0 * R[c] + 2.0 * Rm[c] : 0.0);
-                    if constexpr (XB) m += c == d ? Du[c] : 0.0;
-                    Muu[c][d] = (held[c] || held[d]) ? (c == d ? 1.0 : 0.0) : m;
-                }
-#pragma unroll
-                for (int j = 0; j < NX; ++j) Mus[c][j] = held[c] ? 0.0 : M[gain_sym(j, NX + c, K)];
-#pragma unroll
-                for (int d = 0; d < NU; ++d) Mus[c][NX + d] = (c == d && !held[c]) ? -2.0 * R[c] : 0.0;
-            }
-            ok = gain_chol<NU>(Muu, il);
-            double G[NU][K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                double m[NU], g[NU];
-#pragma unroll
-                for (int c = 0; c < NU; ++c) m[c] = Mus[c][j];
-                gain_solve<NU>(Muu, il, m, g);
-#pragma unroll
-                for (int c = 0; c < NU; ++c) G[c][j] = held[c] ? 0.0 : g[c];
-            }
-            // P_k = M_ss + M_su G_k
-#pragma unroll
-            for (int i = 0; i < K; ++i)
-#pragma unroll
-                for (int j = i; j < K; ++j) {
-                    double s = (j < NX) ? M[gain_sym(i, j, K)] : ((i == j) ? 2.0 * R[i - (i >= NX ? NX : 0)] : 0.0);
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) s += Mus[c][i] * G[c][j];
-                    P[gain_sym(i, j, K)] = s;
-                    chk += gain_nonfinite(s);
-                }
+#define MMPC_SENS_PART 1   // the model, nu_k / lam, M_yy (+ W_k), the held rows, the factor of M_uu, G_k
+#include "sens_lane_stage.inc"
+#define MMPC_SENS_PART 2   // P_k = M_ss + M_su G_k
+#include "sens_lane_stage.inc"
             ok = ok && chk == 0.0;
             if (ok && k < p.n_gain) {
 #pragma unroll
@@ -341,7 +229,7 @@ __host__ __device__ constexpr int gain_group_lds_doubles(int nx, int nu, int N, 
 // The stage records live in LDS (dynamic, gain_group_lds_doubles per instance): the launch takes as many instances per
 // workgroup as fit 160 KB, and a horizon whose single instance does not fit is refused by the host (no HBM scratch).
 // Lanes of a group run in lock step within their wave, so the LDS exchanges need only the compiler-level wave barrier,
-// as in sqp_group.h.
+// as in sqp_group.h.  The instance prologue is part 0 of sens_lane_stage.inc; the phases are this kernel's own.
 extern __shared__ double gain_group_lds[];
 template <class Model, bool EXACT, bool BOUNDED, bool XB = false>
 __global__ __launch_bounds__(64) void gain_group_kernel(const GainParamsOf<XB> p) {
@@ -364,21 +252,8 @@ __global__ __launch_bounds__(64) void gain_group_kernel(const GainParamsOf<XB> p
     const double* w = p.weights + b * p.w_stride;
     const double* tr = p.traj + b * (int64_t)N * NX;
     double* Gb = p.G + b * (int64_t)p.n_gain * (NU * K);
-    double Q[NX], R[NU], Rm[NU], lb[NU], ub[NU];
-    double fin = 0.0;
-#pragma unroll
-    for (int r = 0; r < NX; ++r) {
-        Q[r] = w[r];
-        fin += gain_nonfinite(v[(int64_t)N * K + r]) + gain_nonfinite(Q[r]);
-    }
-#pragma unroll
-    for (int c = 0; c < NU; ++c) {
-        R[c] = w[NX + c];
-        Rm[c] = w[NX + NU + c];
-        fin += gain_nonfinite(p.u_prev[b * NU + c]) + gain_nonfinite(R[c]) + gain_nonfinite(Rm[c]);
-        lb[c] = (BOUNDED && p.u_lb) ? p.u_lb[b * p.b_stride + c] : -INFINITY;
-        ub[c] = (BOUNDED && p.u_ub) ? p.u_ub[b * p.b_stride + c] : INFINITY;
-    }
+#define MMPC_SENS_PART 0   // Q, R, Rm, lb, ub, up, fin
+#include "sens_lane_stage.inc"
     // ---- A ----
     for (int k = l; k < N; k += G) {
         double x[NX], u[NU], xd[NX], fx[NX * NX], fu[NX * NU];

@@ -1321,47 +1321,41 @@ int read_sens_barrier(mmpc_handle* h, const char* what, XbTail* xb) {
     return MMPC_OK;
 }
 
-// ---- feedback gains (mmpc_feedback_gains_batch; gain_sweep.h, DESIGN.md 3i) ----
-struct GainArgs {
+// ---- what the gain and VJP calls share: arguments, check, kernel parameters, variant, staging ----
+struct SensArgs {
     int64_t B = 0;
     const double *V = nullptr, *u_prev = nullptr, *traj = nullptr, *weights = nullptr;
     int64_t weights_stride = 0;
     const double *u_lb = nullptr, *u_ub = nullptr;
     int64_t bounds_stride = 0;
-    int32_t n_pin = 0, n_gain = 0, hessian = 0, kernel = 0;
-    double* G = nullptr;
+    int32_t n_pin = 0, hessian = 0;
     int32_t* status = nullptr;
     hipStream_t stream = nullptr;
 };
-// instances per workgroup of the 16-lane gain kernel: as many as fit 160 KB of LDS, 0 when one does not
-int gain_group_gpw(const mmpc_model_info& mi, bool exact, bool xb) {
-    const size_t inst =
-        static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, exact, xb)) *
-        sizeof(double);
-    return static_cast<int>(std::min<size_t>(kGroupsPerWave, kMaxGroupLds / inst));
-}
-// The one check of a gain call's arguments: pure arithmetic on the arguments and the handle, before any device call.
+// Where a call's own rules stand among the shared ones of check_sens_args: each after the shared rule it followed when
+// the two checks were written out, so that of two bad arguments the one reported stays the same.
+enum class SensRule { kAfterPin, kAfterHessian, kAfterVariant, kAfterInputs };
+// The shared rules of a gain or VJP call's arguments: pure arithmetic on the arguments and the handle, before any
+// device call.  what: the call as the refusals name it ("feedback gains are").  own(SensRule): the call's own rules.
 // *exact: the Hessian the call runs (AUTO: exact wherever the model has second derivatives -- the true derivative is
 // wanted whatever Hessian the solve ran, so this is not resolve_hessian).  *xb: read_sens_barrier's answer.
-int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact, XbTail* xb) {
+template <class Own>
+int check_sens_args(mmpc_handle* h, const SensArgs& a, const char* what, bool* exact, XbTail* xb, Own own) {
     if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
     const mmpc_model_info& mi = h->info;
     const int N = mi.num_shooting_nodes;
     if (a.n_pin < 0 || a.n_pin > N - 1)
         return fail(MMPC_ERR_INVALID_ARG, "n_pin must be 0 .. N - 1 (" + std::to_string(N - 1) + "), got " +
                                               std::to_string(a.n_pin));
-    if (a.n_gain < 1 || a.n_gain > N)
-        return fail(MMPC_ERR_INVALID_ARG, "n_gain must be 1 .. N (" + std::to_string(N) + "), got " +
-                                              std::to_string(a.n_gain));
+    if (int rc = own(SensRule::kAfterPin)) return rc;
     if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
     if (int rc = check_bounds_stride(mi, a.bounds_stride)) return rc;
     if (a.hessian < MMPC_HESSIAN_AUTO || a.hessian > MMPC_HESSIAN_EXACT)
         return fail(MMPC_ERR_INVALID_ARG, "hessian: not an mmpc_hessian value (" + std::to_string(a.hessian) + ")");
-    if (a.kernel < MMPC_GAIN_KERNEL_AUTO || a.kernel > MMPC_GAIN_KERNEL_GROUP)
-        return fail(MMPC_ERR_INVALID_ARG, "kernel: not an mmpc_gain_kernel value (" + std::to_string(a.kernel) + ")");
+    if (int rc = own(SensRule::kAfterHessian)) return rc;
     if (mi.is_linear)
-        return fail(MMPC_ERR_UNSUPPORTED, "feedback gains are not available for a linear-mode model");
-    if (int rc = read_sens_barrier(h, "feedback gains are", xb)) return rc;
+        return fail(MMPC_ERR_UNSUPPORTED, std::string(what) + " not available for a linear-mode model");
+    if (int rc = read_sens_barrier(h, what, xb)) return rc;
     bool has_hess = false;
     with_model(mi.model_id, [&](auto* m) {
         has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
@@ -1370,20 +1364,125 @@ int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact, XbTail* xb) 
     if (a.hessian == MMPC_HESSIAN_EXACT && !has_hess)
         return fail(MMPC_ERR_UNSUPPORTED, "hessian = EXACT: the model has no second derivatives");
     *exact = a.hessian != MMPC_HESSIAN_GAUSS_NEWTON && has_hess;
-    if (a.kernel == MMPC_GAIN_KERNEL_GROUP) {
-        if (mi.num_x + mi.num_u >= kGroupLanes)
-            return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel) needs nx + nu < 16");
-        if (gain_group_gpw(mi, *exact, xb->mu > 0.0) < 1)
-            return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel): the stage records of one instance "
-                                              "exceed 160 KB of LDS at this horizon");
-    }
+    if (int rc = own(SensRule::kAfterVariant)) return rc;
     if (a.B == 0) return MMPC_OK;
     if (!a.V || !a.u_prev || !a.traj || !a.weights) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
-    if (!a.G) return fail(MMPC_ERR_INVALID_ARG, "G_out is NULL");
+    if (int rc = own(SensRule::kAfterInputs)) return rc;
     if (a.weights_stride != 0 && a.weights_stride < mi.num_x + 2 * mi.num_u)
         return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
     if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
     return MMPC_OK;
+}
+// the head of a sensitivity kernel's parameters (SensParams, gain_sweep.h) and the barrier's tail
+template <class Params>
+void fill_sens_params(const mmpc_handle* h, const SensArgs& a, const XbTail& xb, Params& p) {
+    p.xb = xb;
+    p.B = a.B;
+    p.N = h->info.num_shooting_nodes;
+    p.h = h->info.step_size;
+    p.V = a.V;
+    p.u_prev = a.u_prev;
+    p.traj = a.traj;
+    p.weights = a.weights;
+    p.w_stride = a.weights_stride;
+    p.u_lb = a.u_lb;
+    p.u_ub = a.u_ub;
+    p.b_stride = static_cast<int32_t>(a.bounds_stride);
+    p.n_pin = a.n_pin;
+}
+// f(EXACT, BOUNDED, XB) with the three flags of a call lifted to std::bool_constant's: the one place that knows the
+// kernels of a model -- the exact Hessian only where the model has one, and XB implies BOUNDED.
+template <class M, class F>
+int with_sens_variant(bool exact, bool bounded, bool xb, F f) {
+    const auto lift = [&](auto ex) {
+        if (xb) return f(ex, std::true_type{}, std::true_type{});
+        return bounded ? f(ex, std::true_type{}, std::false_type{}) : f(ex, std::false_type{}, std::false_type{});
+    };
+    if constexpr (HasHess<M>::value) {
+        if (exact) return lift(std::true_type{});
+    }
+    return lift(std::false_type{});
+}
+// f() on the handle's device, which is the current one for the call's duration
+template <class F>
+int on_handle_device(mmpc_handle* h, F f) {
+    int dev;
+    if (int rc = resolve_device(h, &dev)) return rc;
+    DeviceGuard g(dev);
+    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
+    return f();
+}
+// The staging of a *_host sensitivity entry, in doubles of the handle's buffer:
+//   V | (extra) | u_prev | traj | weights | u_lb | u_ub | (own) | status,
+// extra and own being the entry's own regions.  Sizes the buffer, copies the six shared inputs to the device on the
+// host stream and points a's inputs, status and stream at the staged copies.  *d: the buffer;  *off_extra, *off_own:
+// where the entry's regions start.  The caller holds the host lock and has the handle's device current.
+int stage_sens_inputs(mmpc_handle* h, SensArgs& a, size_t extra, size_t own, double** d, size_t* off_extra,
+                      size_t* off_own) {
+    const mmpc_model_info& mi = h->info;
+    const size_t B = static_cast<size_t>(a.B), nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
+    const size_t nW = a.weights_stride ? B * static_cast<size_t>(a.weights_stride) : nx + 2 * nu;
+    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
+    const size_t nB = (a.bounds_stride ? B - 1 : 0) * static_cast<size_t>(a.bounds_stride) + nu;
+    const size_t off_V = 0, off_x = off_V + B * NV, off_up = off_x + extra, off_tr = off_up + B * nu;
+    const size_t off_w = off_tr + B * N * nx, off_lb = off_w + nW, off_ub = off_lb + nB, off_o = off_ub + nB;
+    const size_t off_st = off_o + own, total = off_st + (B + 1) / 2;
+    if (int rc = ensure_host_ctx(h, total * sizeof(double))) return rc;
+    double* const b = h->d_buf;
+    hipStream_t s = h->host_stream;
+    MMPC_HIP(hipMemcpyAsync(b + off_V, a.V, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(b + off_up, a.u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(b + off_tr, a.traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
+    MMPC_HIP(hipMemcpyAsync(b + off_w, a.weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
+    if (a.u_lb) MMPC_HIP(hipMemcpyAsync(b + off_lb, a.u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    if (a.u_ub) MMPC_HIP(hipMemcpyAsync(b + off_ub, a.u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
+    a.V = b + off_V;
+    a.u_prev = b + off_up;
+    a.traj = b + off_tr;
+    a.weights = b + off_w;
+    a.u_lb = a.u_lb ? b + off_lb : nullptr;
+    a.u_ub = a.u_ub ? b + off_ub : nullptr;
+    a.status = reinterpret_cast<int32_t*>(b + off_st);
+    a.stream = s;
+    *d = b;
+    *off_extra = off_x;
+    *off_own = off_o;
+    return MMPC_OK;
+}
+
+// ---- feedback gains (mmpc_feedback_gains_batch; gain_sweep.h, DESIGN.md 3i) ----
+struct GainArgs : SensArgs {
+    int32_t n_gain = 0, kernel = 0;
+    double* G = nullptr;
+};
+// instances per workgroup of the 16-lane gain kernel: as many as fit 160 KB of LDS, 0 when one does not
+int gain_group_gpw(const mmpc_model_info& mi, bool exact, bool xb) {
+    const size_t inst =
+        static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes, exact, xb)) *
+        sizeof(double);
+    return static_cast<int>(std::min<size_t>(kGroupsPerWave, kMaxGroupLds / inst));
+}
+// The one check of a gain call's arguments: check_sens_args with the rules of n_gain, kernel and G_out.
+int check_gain_args(mmpc_handle* h, const GainArgs& a, bool* exact, XbTail* xb) {
+    return check_sens_args(h, a, "feedback gains are", exact, xb, [&](SensRule at) -> int {
+        const mmpc_model_info& mi = h->info;
+        const int N = mi.num_shooting_nodes;
+        if (at == SensRule::kAfterPin && (a.n_gain < 1 || a.n_gain > N))
+            return fail(MMPC_ERR_INVALID_ARG, "n_gain must be 1 .. N (" + std::to_string(N) + "), got " +
+                                                  std::to_string(a.n_gain));
+        if (at == SensRule::kAfterHessian && (a.kernel < MMPC_GAIN_KERNEL_AUTO || a.kernel > MMPC_GAIN_KERNEL_GROUP))
+            return fail(MMPC_ERR_INVALID_ARG,
+                        "kernel: not an mmpc_gain_kernel value (" + std::to_string(a.kernel) + ")");
+        if (at == SensRule::kAfterVariant && a.kernel == MMPC_GAIN_KERNEL_GROUP) {
+            if (mi.num_x + mi.num_u >= kGroupLanes)
+                return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel) needs nx + nu < 16");
+            if (gain_group_gpw(mi, *exact, xb->mu > 0.0) < 1)
+                return fail(MMPC_ERR_UNSUPPORTED, "kernel = 2 (the 16-lane kernel): the stage records of one instance "
+                                                  "exceed 160 KB of LDS at this horizon");
+        }
+        if (at == SensRule::kAfterInputs && !a.G) return fail(MMPC_ERR_INVALID_ARG, "G_out is NULL");
+        return MMPC_OK;
+    });
 }
 // The kernel a gain call of B instances runs (measured on one MI355X, tools/feedback_gains_cost.py): the
 // 16-lane kernel while its workgroups are at most two per compute unit -- B <= 2 gpw CUs, gpw = the instances per
@@ -1424,19 +1523,7 @@ int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact, const XbTail& xb
     const bool xbv = xb.mu > 0.0;
     const int kernel = resolve_gain_kernel(h, a.B, exact, xbv, a.kernel);
     GainXbParams p{};
-    p.xb = xb;
-    p.B = a.B;
-    p.N = mi.num_shooting_nodes;
-    p.h = mi.step_size;
-    p.V = a.V;
-    p.u_prev = a.u_prev;
-    p.traj = a.traj;
-    p.weights = a.weights;
-    p.w_stride = a.weights_stride;
-    p.u_lb = a.u_lb;
-    p.u_ub = a.u_ub;
-    p.b_stride = static_cast<int32_t>(a.bounds_stride);
-    p.n_pin = a.n_pin;
+    fill_sens_params(h, a, xb, p);
     p.n_gain = a.n_gain;
     p.G = a.G;
     p.status = a.status;
@@ -1445,36 +1532,21 @@ int launch_gains(mmpc_handle* h, const GainArgs& a, bool exact, const XbTail& xb
                            ? static_cast<size_t>(gain_group_lds_doubles(mi.num_x, mi.num_u, p.N, exact, xbv)) * p.gpw *
                                  sizeof(double)
                            : 0;
-    const bool bounded = a.u_lb || a.u_ub;
     return with_model(mi.model_id, [&](auto* m) {
         using M = std::remove_pointer_t<decltype(m)>;
-        if constexpr (HasHess<M>::value) {
-            if (exact && xbv) return launch_gain_kernels<M, true, true, true>(kernel, p, lds, a.stream);
-            if (exact)
-                return bounded ? launch_gain_kernels<M, true, true>(kernel, p, lds, a.stream)
-                               : launch_gain_kernels<M, true, false>(kernel, p, lds, a.stream);
-        }
-        if (xbv) return launch_gain_kernels<M, false, true, true>(kernel, p, lds, a.stream);
-        return bounded ? launch_gain_kernels<M, false, true>(kernel, p, lds, a.stream)
-                       : launch_gain_kernels<M, false, false>(kernel, p, lds, a.stream);
+        return with_sens_variant<M>(exact, a.u_lb || a.u_ub, xbv, [&](auto ex, auto bd, auto x) {
+            return launch_gain_kernels<M, decltype(ex)::value, decltype(bd)::value, decltype(x)::value>(kernel, p, lds,
+                                                                                                         a.stream);
+        });
     });
 }
 
 // ---- reverse-mode product of the solve (mmpc_solve_vjp_batch; adjoint_sweep.h) ----
-struct VjpArgs {
-    int64_t B = 0;
-    const double *V = nullptr, *u_prev = nullptr, *traj = nullptr, *weights = nullptr;
-    int64_t weights_stride = 0;
-    const double *u_lb = nullptr, *u_ub = nullptr;
-    int64_t bounds_stride = 0;
-    int32_t n_pin = 0;
+struct VjpArgs : SensArgs {
     const double* V_bar = nullptr;
-    int32_t hessian = 0;
     double *x0_bar = nullptr, *u_prev_bar = nullptr, *traj_bar = nullptr, *weights_bar = nullptr, *adj_V = nullptr;
-    int32_t* status = nullptr;
     void* workspace = nullptr;
     uint64_t workspace_bytes = 0;
-    hipStream_t stream = nullptr;
     bool forward() const { return traj_bar || weights_bar || adj_V; }   // else backward-only: no record, no workspace
 };
 // bytes of the record workspace of B instances: ceil(B / 64) blocks of (doubles per lane) x 64, lane-interleaved
@@ -1483,37 +1555,16 @@ uint64_t vjp_workspace_bytes(const mmpc_model_info& mi, int64_t B) {
     return blocks * static_cast<uint64_t>(adjoint_lane_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes)) * 64 *
            sizeof(double);
 }
-// The one check of a VJP call's arguments: pure arithmetic on the arguments and the handle, before any device call
-// (check_gain_args's rules; the host entry brings its own workspace and passes check_workspace = false).
+// The one check of a VJP call's arguments: check_sens_args with the rules of V_bar and the workspace (the host entry
+// brings its own workspace and passes check_workspace = false).
 int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool* exact, XbTail* xb) {
-    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
-    const mmpc_model_info& mi = h->info;
-    const int N = mi.num_shooting_nodes;
-    if (a.n_pin < 0 || a.n_pin > N - 1)
-        return fail(MMPC_ERR_INVALID_ARG, "n_pin must be 0 .. N - 1 (" + std::to_string(N - 1) + "), got " +
-                                              std::to_string(a.n_pin));
-    if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
-    if (int rc = check_bounds_stride(mi, a.bounds_stride)) return rc;
-    if (a.hessian < MMPC_HESSIAN_AUTO || a.hessian > MMPC_HESSIAN_EXACT)
-        return fail(MMPC_ERR_INVALID_ARG, "hessian: not an mmpc_hessian value (" + std::to_string(a.hessian) + ")");
-    if (mi.is_linear) return fail(MMPC_ERR_UNSUPPORTED, "the solve VJP is not available for a linear-mode model");
-    if (int rc = read_sens_barrier(h, "the solve VJP is", xb)) return rc;
-    bool has_hess = false;
-    with_model(mi.model_id, [&](auto* m) {
-        has_hess = HasHess<std::remove_pointer_t<decltype(m)>>::value;
+    const int rc = check_sens_args(h, a, "the solve VJP is", exact, xb, [&](SensRule at) -> int {
+        if (at == SensRule::kAfterInputs && !a.V_bar) return fail(MMPC_ERR_INVALID_ARG, "V_bar is NULL");
         return MMPC_OK;
     });
-    if (a.hessian == MMPC_HESSIAN_EXACT && !has_hess)
-        return fail(MMPC_ERR_UNSUPPORTED, "hessian = EXACT: the model has no second derivatives");
-    *exact = a.hessian != MMPC_HESSIAN_GAUSS_NEWTON && has_hess;
-    if (a.B == 0) return MMPC_OK;
-    if (!a.V || !a.u_prev || !a.traj || !a.weights) return fail(MMPC_ERR_INVALID_ARG, "null input pointer");
-    if (!a.V_bar) return fail(MMPC_ERR_INVALID_ARG, "V_bar is NULL");
-    if (a.weights_stride != 0 && a.weights_stride < mi.num_x + 2 * mi.num_u)
-        return fail(MMPC_ERR_INVALID_ARG, "weights_stride must be 0 or >= nx+2nu");
-    if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
+    if (rc || a.B == 0) return rc;
     if (check_workspace && a.forward()) {
-        const uint64_t need = vjp_workspace_bytes(mi, a.B);
+        const uint64_t need = vjp_workspace_bytes(h->info, a.B);
         if (!a.workspace)
             return fail(MMPC_ERR_INVALID_ARG, "workspace is NULL: traj_bar, weights_bar and adj_V need " +
                                                   std::to_string(need) + " bytes (mmpc_solve_vjp_workspace_bytes)");
@@ -1526,21 +1577,8 @@ int check_vjp_args(mmpc_handle* h, const VjpArgs& a, bool check_workspace, bool*
 // a VJP call whose arguments check_vjp_args has passed, B > 0, device pointers, on the current device: one launch,
 // stream-ordered, no allocation, no synchronisation
 int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact, const XbTail& xb) {
-    const mmpc_model_info& mi = h->info;
     AdjointXbParams p{};
-    p.xb = xb;
-    p.B = a.B;
-    p.N = mi.num_shooting_nodes;
-    p.h = mi.step_size;
-    p.V = a.V;
-    p.u_prev = a.u_prev;
-    p.traj = a.traj;
-    p.weights = a.weights;
-    p.w_stride = a.weights_stride;
-    p.u_lb = a.u_lb;
-    p.u_ub = a.u_ub;
-    p.b_stride = static_cast<int32_t>(a.bounds_stride);
-    p.n_pin = a.n_pin;
+    fill_sens_params(h, a, xb, p);
     p.V_bar = a.V_bar;
     p.x0_bar = a.x0_bar;
     p.u_prev_bar = a.u_prev_bar;
@@ -1549,22 +1587,14 @@ int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact, const XbTail& xb) {
     p.adj_V = a.adj_V;
     p.status = a.status;
     p.ws = a.forward() ? static_cast<double*>(a.workspace) : nullptr;
-    const bool bounded = a.u_lb || a.u_ub;
-    const auto launch = [&](auto* k) -> int {
-        k<<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
-        MMPC_HIP(hipGetLastError());
-        return MMPC_OK;
-    };
-    return with_model(mi.model_id, [&](auto* m) {
+    return with_model(h->info.model_id, [&](auto* m) {
         using M = std::remove_pointer_t<decltype(m)>;
-        if constexpr (HasHess<M>::value) {
-            if (exact && xb.mu > 0.0) return launch(&adjoint_lane_kernel<M, true, true, true>);
-            if (exact)
-                return bounded ? launch(&adjoint_lane_kernel<M, true, true>)
-                               : launch(&adjoint_lane_kernel<M, true, false>);
-        }
-        if (xb.mu > 0.0) return launch(&adjoint_lane_kernel<M, false, true, true>);
-        return bounded ? launch(&adjoint_lane_kernel<M, false, true>) : launch(&adjoint_lane_kernel<M, false, false>);
+        return with_sens_variant<M>(exact, a.u_lb || a.u_ub, xb.mu > 0.0, [&](auto ex, auto bd, auto x) -> int {
+            adjoint_lane_kernel<M, decltype(ex)::value, decltype(bd)::value, decltype(x)::value>
+                <<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
+            MMPC_HIP(hipGetLastError());
+            return MMPC_OK;
+        });
     });
 }
 
@@ -1899,18 +1929,13 @@ int mmpc_feedback_gains_batch(mmpc_handle* h, int64_t B, const double* V, const 
                               const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
                               int64_t bounds_stride, int32_t n_pin, int32_t n_gain, int32_t hessian, int32_t kernel,
                               double* G_out, int32_t* gain_status, void* stream) {
-    const GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian,
-                     kernel, G_out, gain_status, reinterpret_cast<hipStream_t>(stream)};
+    const GainArgs a{{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian,
+                      gain_status, reinterpret_cast<hipStream_t>(stream)}, n_gain, kernel, G_out};
     bool exact = false;
     XbTail xb;
     if (int rc = check_gain_args(h, a, &exact, &xb)) return rc;
     if (B == 0) return MMPC_OK;
-    int dev;
-    int rc = resolve_device(h, &dev);
-    if (rc) return rc;
-    DeviceGuard g(dev);
-    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_gains(h, a, exact, xb);
+    return on_handle_device(h, [&] { return launch_gains(h, a, exact, xb); });
 }
 
 int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev,
@@ -1918,52 +1943,28 @@ int mmpc_feedback_gains_batch_host(mmpc_handle* h, int64_t B, const double* V, c
                                    const double* u_lb, const double* u_ub, int64_t bounds_stride, int32_t n_pin,
                                    int32_t n_gain, int32_t hessian, int32_t kernel, double* G_out,
                                    int32_t* gain_status) {
-    GainArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, n_gain, hessian, kernel,
-               G_out, gain_status};
+    GainArgs a{{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian}, n_gain,
+               kernel, G_out};
     bool exact = false;
     XbTail xb;
     if (int rc = check_gain_args(h, a, &exact, &xb)) return rc;   // before weights_stride and bounds_stride size a copy
     if (B == 0) return MMPC_OK;
     std::lock_guard<std::mutex> lk(h->host_mu);
-    const mmpc_model_info& mi = h->info;
-    const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v;
-    const size_t nW = weights_stride ? static_cast<size_t>(B) * static_cast<size_t>(weights_stride) : nx + 2 * nu;
-    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
-    const size_t nB = (bounds_stride ? static_cast<size_t>(B) - 1 : 0) * static_cast<size_t>(bounds_stride) + nu;
-    const size_t nG = static_cast<size_t>(B) * static_cast<size_t>(n_gain) * nu * (nx + nu);
-    const size_t off_V = 0, off_up = off_V + B * NV, off_tr = off_up + B * nu, off_w = off_tr + B * N * nx;
-    const size_t off_lb = off_w + nW, off_ub = off_lb + nB, off_G = off_ub + nB, off_st = off_G + nG;
-    const size_t total = off_st + (B + 1) / 2;
-    int dev;
-    int rc = resolve_device(h, &dev);
-    if (rc) return rc;
-    DeviceGuard g(dev);
-    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    rc = ensure_host_ctx(h, total * sizeof(double));
-    if (rc) return rc;
-    double* d = h->d_buf;
-    hipStream_t s = h->host_stream;
-    MMPC_HIP(hipMemcpyAsync(d + off_V, V, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_up, u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_tr, traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_w, weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
-    int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
-    a.V = d + off_V;
-    a.u_prev = d + off_up;
-    a.traj = d + off_tr;
-    a.weights = d + off_w;
-    a.u_lb = u_lb ? d + off_lb : nullptr;
-    a.u_ub = u_ub ? d + off_ub : nullptr;
-    a.G = d + off_G;
-    a.status = dst;
-    a.stream = s;
-    if ((rc = launch_gains(h, a, exact, xb))) return rc;
-    MMPC_HIP(hipMemcpyAsync(G_out, d + off_G, nG * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (gain_status) MMPC_HIP(hipMemcpyAsync(gain_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MMPC_HIP(hipStreamSynchronize(s));
-    return MMPC_OK;
+    return on_handle_device(h, [&]() -> int {
+        const mmpc_model_info& mi = h->info;
+        const size_t nu = mi.num_u, nG = static_cast<size_t>(B) * static_cast<size_t>(n_gain) * nu * (mi.num_x + nu);
+        double* d;
+        size_t off_x, off_G;
+        if (int rc = stage_sens_inputs(h, a, 0, nG, &d, &off_x, &off_G)) return rc;
+        a.G = d + off_G;
+        if (int rc = launch_gains(h, a, exact, xb)) return rc;
+        hipStream_t s = a.stream;
+        MMPC_HIP(hipMemcpyAsync(G_out, d + off_G, nG * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (gain_status)
+            MMPC_HIP(hipMemcpyAsync(gain_status, a.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MMPC_HIP(hipStreamSynchronize(s));
+        return MMPC_OK;
+    });
 }
 
 int mmpc_solve_vjp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes) {
@@ -1977,19 +1978,14 @@ int mmpc_solve_vjp_batch(mmpc_handle* h, int64_t B, const double* V, const doubl
                          int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian, double* x0_bar,
                          double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V, int32_t* vjp_status,
                          void* workspace, uint64_t workspace_bytes, void* stream) {
-    const VjpArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, V_bar, hessian,
-                    x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status, workspace, workspace_bytes,
-                    reinterpret_cast<hipStream_t>(stream)};
+    const VjpArgs a{{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian,
+                     vjp_status, reinterpret_cast<hipStream_t>(stream)},
+                    V_bar, x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, workspace, workspace_bytes};
     bool exact = false;
     XbTail xb;
     if (int rc = check_vjp_args(h, a, true, &exact, &xb)) return rc;
     if (B == 0) return MMPC_OK;
-    int dev;
-    int rc = resolve_device(h, &dev);
-    if (rc) return rc;
-    DeviceGuard g(dev);
-    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    return launch_vjp(h, a, exact, xb);
+    return on_handle_device(h, [&] { return launch_vjp(h, a, exact, xb); });
 }
 
 int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
@@ -1997,69 +1993,48 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
                               int64_t bounds_stride, int32_t n_pin, const double* V_bar, int32_t hessian,
                               double* x0_bar, double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V,
                               int32_t* vjp_status) {
-    VjpArgs a{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, V_bar, hessian,
-              x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V, vjp_status};
+    VjpArgs a{{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian},
+              V_bar, x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V};
     bool exact = false;
     XbTail xb;
     if (int rc = check_vjp_args(h, a, false, &exact, &xb)) return rc;   // before the strides size a copy
     if (B == 0) return MMPC_OK;
     std::lock_guard<std::mutex> lk(h->host_mu);
-    const mmpc_model_info& mi = h->info;
-    const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v, nw = nx + 2 * nu;
-    const size_t nW = weights_stride ? static_cast<size_t>(B) * static_cast<size_t>(weights_stride) : nw;
-    // staged bound doubles: the caller's buffer holds (B - 1) stride + nu of them and is never read past that
-    const size_t nB = (bounds_stride ? static_cast<size_t>(B) - 1 : 0) * static_cast<size_t>(bounds_stride) + nu;
-    const size_t nWs = a.forward() ? vjp_workspace_bytes(mi, B) / sizeof(double) : 0;
-    const size_t off_V = 0, off_Vb = off_V + B * NV, off_up = off_Vb + B * NV, off_tr = off_up + B * nu;
-    const size_t off_w = off_tr + B * N * nx, off_lb = off_w + nW, off_ub = off_lb + nB, off_x0b = off_ub + nB;
-    const size_t off_upb = off_x0b + B * nx, off_trb = off_upb + B * nu, off_wb = off_trb + B * N * nx;
-    const size_t off_a = off_wb + B * nw, off_ws = off_a + B * NV, off_st = off_ws + nWs;
-    const size_t total = off_st + (B + 1) / 2;
-    int dev;
-    int rc = resolve_device(h, &dev);
-    if (rc) return rc;
-    DeviceGuard g(dev);
-    if (g.err) return fail(MMPC_ERR_NO_DEVICE, "cannot select device");
-    rc = ensure_host_ctx(h, total * sizeof(double));
-    if (rc) return rc;
-    double* d = h->d_buf;
-    hipStream_t s = h->host_stream;
-    MMPC_HIP(hipMemcpyAsync(d + off_V, V, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_Vb, V_bar, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_up, u_prev, B * nu * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_tr, traj, B * N * nx * sizeof(double), hipMemcpyHostToDevice, s));
-    MMPC_HIP(hipMemcpyAsync(d + off_w, weights, nW * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_lb) MMPC_HIP(hipMemcpyAsync(d + off_lb, u_lb, nB * sizeof(double), hipMemcpyHostToDevice, s));
-    if (u_ub) MMPC_HIP(hipMemcpyAsync(d + off_ub, u_ub, nB * sizeof(double), hipMemcpyHostToDevice, s));
-    int32_t* dst = reinterpret_cast<int32_t*>(d + off_st);
-    a.V = d + off_V;
-    a.V_bar = d + off_Vb;
-    a.u_prev = d + off_up;
-    a.traj = d + off_tr;
-    a.weights = d + off_w;
-    a.u_lb = u_lb ? d + off_lb : nullptr;
-    a.u_ub = u_ub ? d + off_ub : nullptr;
-    a.x0_bar = x0_bar ? d + off_x0b : nullptr;
-    a.u_prev_bar = u_prev_bar ? d + off_upb : nullptr;
-    a.traj_bar = traj_bar ? d + off_trb : nullptr;
-    a.weights_bar = weights_bar ? d + off_wb : nullptr;
-    a.adj_V = adj_V ? d + off_a : nullptr;
-    a.status = dst;
-    a.workspace = nWs ? d + off_ws : nullptr;
-    a.workspace_bytes = nWs * sizeof(double);
-    a.stream = s;
-    if ((rc = launch_vjp(h, a, exact, xb))) return rc;
-    const auto back = [&](double* dst_host, size_t off, size_t n) {
-        return dst_host ? hipMemcpyAsync(dst_host, d + off, n * sizeof(double), hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    MMPC_HIP(back(x0_bar, off_x0b, B * nx));
-    MMPC_HIP(back(u_prev_bar, off_upb, B * nu));
-    MMPC_HIP(back(traj_bar, off_trb, B * N * nx));
-    MMPC_HIP(back(weights_bar, off_wb, B * nw));
-    MMPC_HIP(back(adj_V, off_a, B * NV));
-    if (vjp_status) MMPC_HIP(hipMemcpyAsync(vjp_status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MMPC_HIP(hipStreamSynchronize(s));
-    return MMPC_OK;
+    return on_handle_device(h, [&]() -> int {
+        const mmpc_model_info& mi = h->info;
+        const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v, nw = nx + 2 * nu;
+        const size_t nWs = a.forward() ? vjp_workspace_bytes(mi, B) / sizeof(double) : 0;
+        // own regions: V_bar after V;  x0_bar | u_prev_bar | traj_bar | weights_bar | adj_V | the records after u_ub
+        double* d;
+        size_t off_Vb, off_x0b;
+        const size_t n_own = B * nx + B * nu + B * N * nx + B * nw + B * NV + nWs;
+        if (int rc = stage_sens_inputs(h, a, B * NV, n_own, &d, &off_Vb, &off_x0b)) return rc;
+        const size_t off_upb = off_x0b + B * nx, off_trb = off_upb + B * nu, off_wb = off_trb + B * N * nx;
+        const size_t off_a = off_wb + B * nw, off_ws = off_a + B * NV;
+        hipStream_t s = a.stream;
+        MMPC_HIP(hipMemcpyAsync(d + off_Vb, V_bar, B * NV * sizeof(double), hipMemcpyHostToDevice, s));
+        a.V_bar = d + off_Vb;
+        a.x0_bar = x0_bar ? d + off_x0b : nullptr;
+        a.u_prev_bar = u_prev_bar ? d + off_upb : nullptr;
+        a.traj_bar = traj_bar ? d + off_trb : nullptr;
+        a.weights_bar = weights_bar ? d + off_wb : nullptr;
+        a.adj_V = adj_V ? d + off_a : nullptr;
+        a.workspace = nWs ? d + off_ws : nullptr;
+        a.workspace_bytes = nWs * sizeof(double);
+        if (int rc = launch_vjp(h, a, exact, xb)) return rc;
+        const auto back = [&](double* dst_host, size_t off, size_t n) {
+            return dst_host ? hipMemcpyAsync(dst_host, d + off, n * sizeof(double), hipMemcpyDeviceToHost, s)
+                            : hipSuccess;
+        };
+        MMPC_HIP(back(x0_bar, off_x0b, B * nx));
+        MMPC_HIP(back(u_prev_bar, off_upb, B * nu));
+        MMPC_HIP(back(traj_bar, off_trb, B * N * nx));
+        MMPC_HIP(back(weights_bar, off_wb, B * nw));
+        MMPC_HIP(back(adj_V, off_a, B * NV));
+        if (vjp_status) MMPC_HIP(hipMemcpyAsync(vjp_status, a.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MMPC_HIP(hipStreamSynchronize(s));
+        return MMPC_OK;
+    });
 }
 
 int mmpc_resolve_kkt_solver(const mmpc_handle* h, int64_t B, int32_t* solver) {

@@ -11,7 +11,7 @@ import pytest
 
 import oracle_lib as oracle
 from conftest import WEIGHTS_CFG
-from test_gpu_feedback_gains import gains, held_mask, stage_data
+from sens_reference import gains, held_mask, stage_data
 
 H = 0.002
 W_2L = np.array(WEIGHTS_CFG)

@@ -1,7 +1,7 @@
 """GPU: feedback gains along the plan, G_k = d u_k* / d(x_k, u_{k-1}) (mmpc_feedback_gains_batch).
 
-The reference (this module, numpy over oracle_lib's Jacobians and oracle_nlp_hess) is the DENSE sensitivity of the tail
-problem, not a second Riccati recursion.  Tail problem from stage k: the stages k..N-1 of the NLP from x_k = x with
+The reference (tests/sens_reference.py, numpy over oracle_lib's Jacobians and oracle_nlp_hess) is the DENSE sensitivity
+of the tail problem, not a second Riccati recursion.  Tail problem from stage k: the stages k..N-1 of the NLP from x_k = x with
 u_{k-1} = v.  Linearised at the plan, dx_{j+1} = A_j dx_j + B_j du_j, so every (dx_j, du_j) is linear in the parameters
 p = (dx, dv) and the unknowns dU = (du_k .. du_{N-1}); the Lagrangian's Hessian in these variables is the sum of the
 stage blocks (nlp_hess_l with the multipliers of tests/test_kkt_certificate.py::_certify, or their Gauss-Newton part)
@@ -37,6 +37,7 @@ import pytest
 
 import oracle_lib as oracle
 from conftest import WEIGHTS_CFG
+from sens_reference import gains, gains_batch, held_mask
 from test_gpu_bounded_shapes import UB, W_EXO
 
 pytestmark = pytest.mark.gpu
@@ -50,111 +51,6 @@ WEIGHTS = {"two_link_arm": W_2L, "exo_arm": W_EXO}
 TOL = 1e-10
 
 
-# ---------------------------------------------------------------- the reference
-
-
-def _jac(model, x, u):
-    return (oracle.exo_jac if model == oracle.EXO else oracle.two_link_jac)(x, u)
-
-
-def stage_data(model, N, h, V, up, tr, w, exact):
-    """A_k, B_k and the (x_k, u_k) Hessian blocks of the Lagrangian at V, exact or Gauss-Newton"""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    Q, R, Rm = w[:nx], w[nx:nx + nu], w[nx + nu:]
-    Vs = V[:-nx].reshape(N, K)
-    A, B, e = [], [], []
-    for k in range(N):
-        Ac, Bc, xd = _jac(model, Vs[k, :nx], Vs[k, nx:])
-        A.append(np.eye(nx) + h * Ac)
-        B.append(h * Bc)
-        e.append(Vs[k, :nx] + h * xd - tr[k])
-    if exact:
-        lam = np.zeros((N, nx))   # lam_k = A_{k+1}^T (2 Q e_{k+1} + lam_{k+1}), lam_{N-1} = 0
-        for k in range(N - 2, -1, -1):
-            lam[k] = A[k + 1].T @ (2 * Q * e[k + 1] + lam[k + 1])
-        blocks = oracle.nlp_hess(N, h, V, up, tr, w, 1.0, lam, model=model)
-    else:
-        blocks = np.zeros((N, K, K))
-        for k in range(N):
-            JF = np.hstack([A[k], B[k]])
-            blocks[k] = 2 * JF.T @ (Q[:, None] * JF)
-            blocks[k, nx:, nx:] += np.diag(2 * R + 2 * Rm + (2 * R if k + 1 < N else 0))
-    return A, B, blocks
-
-
-def held_mask(model, N, V, lb, ub, n_pin):
-    """[N, nu] bool: control on a finite bound bit for bit, or committed"""
-    nx, nu = oracle.DIMS[model]
-    U = V[:-nx].reshape(N, nx + nu)[:, nx:]
-    held = np.zeros((N, nu), bool)
-    held[:n_pin] = True
-    if lb is not None:
-        held |= (np.abs(lb) < 1e19)[None, :] & (U == lb[None, :])
-    if ub is not None:
-        held |= (np.abs(ub) < 1e19)[None, :] & (U == ub[None, :])
-    return held
-
-
-def tail_system(model, N, k, A, B, blocks, w):
-    """H_UU [(N-k) nu]^2 and H_Up [(N-k) nu, K] of the tail problem from stage k, no control removed"""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    R = w[nx:nx + nu]
-    n = (N - k) * nu
-    Su = np.zeros((nx, n))
-    Sp = np.eye(nx)
-    HUU = np.zeros((n, n))
-    HUp = np.zeros((n, K))
-    for j in range(k, N):
-        Yu = np.zeros((K, n))    # (dx_j, du_j) as functions of dU and of dx
-        Yu[:nx] = Su
-        Yu[nx + np.arange(nu), (j - k) * nu + np.arange(nu)] = 1.0
-        Yp = np.zeros((K, nx))
-        Yp[:nx] = Sp
-        HUU += Yu.T @ blocks[j] @ Yu
-        HUp[:, :nx] += Yu.T @ blocks[j] @ Yp
-        Su, Sp = A[j] @ Su + B[j] @ Yu[nx:], A[j] @ Sp
-    for j in range(k + 1, N):
-        for c in range(nu):
-            a, b = (j - k) * nu + c, (j - 1 - k) * nu + c
-            HUU[a, b] -= 2 * R[c]
-            HUU[b, a] -= 2 * R[c]
-    for c in range(nu):
-        HUp[c, nx + c] -= 2 * R[c]
-    return 0.5 * (HUU + HUU.T), HUp
-
-
-def gains(model, N, h, V, up, tr, w, exact, lb=None, ub=None, n_pin=0, stages=None, min_eig=None):
-    """G_k [nu, nx + nu] for k in stages (default all N), one instance.  min_eig: a list that receives, per stage,
-    the smallest eigenvalue of the free part of H_UU over its largest."""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    w = np.asarray(w, dtype=np.float64)
-    A, B, blocks = stage_data(model, N, h, V, up, tr, w, exact)
-    held = held_mask(model, N, V, None if lb is None else np.asarray(lb, dtype=np.float64),
-                     None if ub is None else np.asarray(ub, dtype=np.float64), n_pin)
-    stages = range(N) if stages is None else stages
-    out = np.zeros((len(stages), nu, K))
-    for i, k in enumerate(stages):
-        HUU, HUp = tail_system(model, N, k, A, B, blocks, w)
-        free = ~held[k:].ravel()
-        dU = np.zeros((free.size, K))
-        if free.any():
-            Hf = HUU[np.ix_(free, free)]
-            dU[free] = -np.linalg.solve(Hf, HUp[free])
-            if min_eig is not None:
-                ev = np.linalg.eigvalsh(Hf)
-                min_eig.append(ev.min() / ev.max())
-        out[i] = dU[:nu]
-    return out
-
-
-def gains_batch(model, N, h, V, up, tr, w, exact, lb=None, ub=None, n_pin=0, stages=None):
-    """gains() for every instance: [B, len(stages), nu, nx + nu]; w [nw] shared, lb / ub [nu] shared or [B, nu]"""
-    row = lambda a, b: None if a is None else (np.asarray(a, dtype=np.float64)[b] if np.ndim(a) == 2 else a)  # noqa: E731
-    return np.stack([gains(model, N, h, V[b], up[b], tr[b], w, exact, row(lb, b), row(ub, b), n_pin, stages)
-                     for b in range(V.shape[0])])
 
 
 # ---------------------------------------------------------------- the cases

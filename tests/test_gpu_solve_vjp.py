@@ -1,7 +1,7 @@
 """GPU: reverse-mode products of the solve, theta_bar = (d V* / d theta)^T V_bar (mmpc_solve_vjp_batch).
 
 V* comes from the GPU solve, V_bar is standard normal from a fixed seed, the reference is the dense KKT solve of
-tests/test_solve_vjp_reference.py (dense_vjp), not a second Riccati recursion.  Inputs as in
+tests/sens_reference.py (dense_vjp), not a second Riccati recursion.  Inputs as in
 tests/test_gpu_feedback_gains.py: oracle.synth(20250213, 0, B, N, 0.002), WEIGHTS_CFG and W_EXO.  Every comparison with
 the reference is per instance and per output array (x0_bar, u_prev_bar, traj_bar, weights_bar, adj_V) at
 1e-10 max(1, max |ref|), the project's standing GPU-versus-reference tolerance.
@@ -31,9 +31,8 @@ the reference is per instance and per output array (x0_bar, u_prev_bar, traj_bar
 import numpy as np
 import pytest
 
-from test_gpu_feedback_gains import (BOUNDED, DIMS, H, OMODEL, SEED, SHAPES, W_2L, WEIGHTS, Ctx, _id, dev, held_mask,
-                                     hess_id)
-from test_solve_vjp_reference import OUT, dense_vjp_batch, fd_delta
+from sens_reference import OUT, dense_vjp_batch, fd_delta, held_mask
+from test_gpu_feedback_gains import BOUNDED, DIMS, H, OMODEL, SEED, SHAPES, W_2L, WEIGHTS, Ctx, _id, dev, hess_id
 
 pytestmark = pytest.mark.gpu
 

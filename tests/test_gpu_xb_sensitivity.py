@@ -40,11 +40,11 @@ import pytest
 
 import oracle_lib as oracle
 from conftest import ROOT
+from sens_reference import CAP_DEFAULT, OUT, xb_dense_gains_batch, xb_dense_vjp_batch
 from test_gpu_bounded_shapes import XB
 from test_gpu_feedback_gains import DIMS, OMODEL, WEIGHTS, W_2L, dev, gpu_gains, hess_id
 from test_gpu_solve_vjp import gpu_vjp
-from test_xb_sensitivity_reference import (CAP_DEFAULT, CAP_PIN, FD, FLOOR, H, OUT, SEED, arr, fd_errors, fd_of_solves,
-                                           xb_dense_gains_batch, xb_dense_vjp_batch, xb_recursion)
+from test_xb_sensitivity_reference import CAP_PIN, FD, FLOOR, H, SEED, arr, fd_errors, fd_of_solves, xb_recursion
 
 pytestmark = pytest.mark.gpu
 
@@ -451,7 +451,7 @@ def test_autograd_on_a_state_bounded_solver(ctx):
         d[i] = 1e-5
         fx[:, i] = (u0_sum(x0 + d, wrows) - u0_sum(x0 - d, wrows)) / 2e-5
         dq = np.zeros(nx + 2 * nu)
-        dq[i] = 1e-5 * W_2L[i]   # relative to the weight's own size (fd_delta of test_solve_vjp_reference.py)
+        dq[i] = 1e-5 * W_2L[i]   # relative to the weight's own size (fd_delta of sens_reference.py)
         fq[:, i] = (u0_sum(x0, wrows + dq) - u0_sum(x0, wrows - dq)) / (2 * dq[i])
     s.close()
     ex = (np.abs(fx - gx).max(1) / np.maximum(1.0, np.abs(gx).max(1))).max()

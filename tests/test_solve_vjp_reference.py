@@ -1,6 +1,6 @@
 """CPU: the definition of the solve's reverse-mode product (mmpc_solve_vjp_batch; include/mmpc.h).
 
-This module is the numpy restatement of the definition, on stage_data / held_mask of tests/test_gpu_feedback_gains.py:
+This module is the numpy restatement of the definition, on stage_data / held_mask of tests/sens_reference.py:
 
 * dense_vjp: the dense KKT solve for (a, b) -- L_zz a + g_z^T b = V_bar_z, g_z a = 0 with a = 0 on x_0 and on held
   controls -- and every output by the implicit function theorem from the dense blocks (the reference of the GPU tests);
@@ -20,72 +20,12 @@ import pytest
 
 import oracle_lib as oracle
 from conftest import WEIGHTS_CFG
-from test_gpu_feedback_gains import _jac, held_mask, stage_data
+from sens_reference import OUT, _residuals, _weight_sums, dense_vjp, fd_delta, held_mask, stage_data
 
 H = 0.002
 SEED = 20250213
 W_2L = np.array(WEIGHTS_CFG)
 W_EXO = np.array([10.0] * 4 + [1.0] * 4 + [1.0] * 4 + [0.01] * 4)
-OUT = ("x0_bar", "u_prev_bar", "traj_bar", "weights_bar", "adj_V")
-
-
-def _residuals(model, N, h, V, tr):
-    """e_k = F(x_k, u_k) - r_k [N, nx]"""
-    nx, nu = oracle.DIMS[model]
-    Vs = V[:-nx].reshape(N, nx + nu)
-    return np.stack([Vs[k, :nx] + h * _jac(model, Vs[k, :nx], Vs[k, nx:])[2] - tr[k] for k in range(N)])
-
-
-def _weight_sums(model, N, V, up, e, a, ax_next):
-    """(Q_bar | R_bar | Rm_bar) from the direction a [NV] and a_{x,k+1} [N, nx]"""
-    nx, nu = oracle.DIMS[model]
-    U = V[:-nx].reshape(N, nx + nu)[:, nx:]
-    aU = a[:-nx].reshape(N, nx + nu)[:, nx:]
-    dU = U - np.vstack([up[None, :], U[:-1]])
-    daU = aU - np.vstack([np.zeros((1, nu)), aU[:-1]])
-    return np.concatenate([-2 * (e * ax_next).sum(0), -2 * (dU * daU).sum(0), -2 * (U * aU).sum(0)])
-
-
-def dense_vjp(model, N, h, V, up, tr, w, Vbar, exact, lb=None, ub=None, n_pin=0):
-    """every output of the definition for one instance, from one dense KKT solve"""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    NV = V.size
-    w = np.asarray(w, dtype=np.float64)
-    Q, R = w[:nx], w[nx:nx + nu]
-    A, B, blocks = stage_data(model, N, h, V, up, tr, w, exact)
-    held = held_mask(model, N, V, None if lb is None else np.asarray(lb, dtype=np.float64),
-                     None if ub is None else np.asarray(ub, dtype=np.float64), n_pin)
-    Hm = np.zeros((NV, NV))   # L_VV: the stage blocks and the -2R couplings of consecutive controls
-    Gz = np.zeros((N * nx, NV))   # the defects' Jacobian: F(x_k, u_k) - x_{k+1}
-    for k in range(N):
-        Hm[k * K:(k + 1) * K, k * K:(k + 1) * K] = blocks[k]
-        Gz[k * nx:(k + 1) * nx, k * K:(k + 1) * K] = np.hstack([A[k], B[k]])
-        Gz[k * nx + np.arange(nx), (k + 1) * K + np.arange(nx)] = -1.0
-        if k >= 1:
-            i, j = k * K + nx + np.arange(nu), (k - 1) * K + nx + np.arange(nu)
-            Hm[i, j] -= 2 * R
-            Hm[j, i] -= 2 * R
-    free = np.ones(NV, bool)
-    free[:nx] = False
-    for k in range(N):
-        free[k * K + nx:(k + 1) * K] = ~held[k]
-    nf, ng = int(free.sum()), N * nx
-    KKT = np.zeros((nf + ng, nf + ng))
-    KKT[:nf, :nf] = Hm[np.ix_(free, free)]
-    KKT[nf:, :nf] = Gz[:, free]
-    KKT[:nf, nf:] = Gz[:, free].T
-    sol = np.linalg.solve(KKT, np.concatenate([Vbar[free], np.zeros(ng)]))
-    a = np.zeros(NV)
-    a[free] = sol[:nf]
-    b = sol[nf:]
-    # theta_bar = V_bar_theta - (d grad_z L / d theta)^T a - (d g / d theta)^T b
-    x0_bar = Vbar[:nx] - Hm[:, :nx].T @ a - Gz[:, :nx].T @ b
-    u_prev_bar = 2 * R * a[nx:K]
-    ax_next = np.stack([np.hstack([A[k], B[k]]) @ a[k * K:(k + 1) * K] for k in range(N)])   # J_k a_{y,k}
-    e = _residuals(model, N, h, V, tr)
-    return dict(x0_bar=x0_bar, u_prev_bar=u_prev_bar, traj_bar=2 * Q[None, :] * ax_next,
-                weights_bar=_weight_sums(model, N, V, up, e, a, ax_next), adj_V=a)
 
 
 def riccati_vjp(model, N, h, V, up, tr, w, Vbar, exact, lb=None, ub=None, n_pin=0):
@@ -135,14 +75,6 @@ def riccati_vjp(model, N, h, V, up, tr, w, Vbar, exact, lb=None, ub=None, n_pin=
                 weights_bar=_weight_sums(model, N, V, up, e, a, ax_next), adj_V=a)
 
 
-def dense_vjp_batch(model, N, h, V, up, tr, w, Vbar, exact, lb=None, ub=None, n_pin=0):
-    """dense_vjp for every instance, stacked; w [nw] shared or [B, nw], lb / ub [nu] shared or [B, nu]"""
-    row = lambda a, b: None if a is None else (np.asarray(a, dtype=np.float64)[b] if np.ndim(a) == 2 else a)  # noqa: E731
-    rows = [dense_vjp(model, N, h, V[b], up[b], tr[b], row(w, b), Vbar[b], exact, row(lb, b), row(ub, b), n_pin)
-            for b in range(V.shape[0])]
-    return {k: np.stack([r[k] for r in rows]) for k in OUT}
-
-
 # ---------------------------------------------------------------- the cases
 PM2 = (np.array([-2.0, -2.0]), np.array([2.0, 2.0]))
 CASES = [(oracle.TWO_LINK, 1, None, (0, 0)), (oracle.TWO_LINK, 5, None, (0, 0)), (oracle.TWO_LINK, 17, PM2, (1, 24)),
@@ -165,13 +97,6 @@ def solved(model, N, bounds):
             arr.setflags(write=False)
         _solved[key] = (w, lb, ub, x0, up, tr, o["V"], Vbar)
     return _solved[key]
-
-
-def fd_delta(name, theta):
-    """the step of a central difference in an input entry, 1e-4 relative: to the entry's own size for a weight (V*
-    depends on the weights through their ratios, and Rm = 0.01 moved by 1e-4 would be a 1 % step with a visible
-    third-order term), to max(1, |theta|) for x0, u_prev and traj (physical quantities of order 1, some of them 0)"""
-    return 1e-4 * (np.abs(theta) if name == "weights_bar" else np.maximum(1.0, np.abs(theta)))
 
 
 @pytest.mark.parametrize("model,N,bounds,n_held", CASES)

@@ -1,16 +1,16 @@
 """CPU: the definition of the feedback gains and the solve VJP under the sensitivity barrier of a state-bounded handle
 (mmpc_set_sensitivity_barrier; include/mmpc.h).
 
-This module is the numpy restatement of the definition and its dense reference; the GPU tests import both.
+This module is the numpy restatement of the definition (xb_recursion); its dense reference (the other names below)
+lives in tests/sens_reference.py; the GPU tests import both.
 
 * barrier_terms: beta = 2 mu (1 / s_u - 1 / s_l) and D = min(2 mu (1 / s_l^2 + 1 / s_u^2), cap) of x_{k+1} and u_k;
-* xb_stage_data: stage_data of tests/test_gpu_feedback_gains.py with beta in the multiplier recursion
+* xb_stage_data: stage_data of tests/sens_reference.py with beta in the multiplier recursion
   (lam_{N-1} = beta(x_N), lam_{k-1} = A_k^T nu_k + beta(x_k); Gauss-Newton ignores beta);
 * xb_recursion: the recursion of the header, term for term (P_{k+1}[x, x] += diag D(x_{k+1}) in place before C^T P C,
   M_uu += diag D(u_k)), the gains and every VJP output -- what the kernels run;
-* xb_dense_gains: the tail system of test_gpu_feedback_gains.py with Su_{j+1}^T D Su_{j+1} / Su_{j+1}^T D Sp_{j+1} added
-  per stage and D_u on the control diagonal; xb_dense_vjp: the dense KKT solve of test_solve_vjp_reference.py with D
-  added to L_zz.  No control is held by bit-equality; stages k < n_pin are held.
+* xb_dense_gains: the tail system (tail_system) with Su_{j+1}^T D Su_{j+1} / Su_{j+1}^T D Sp_{j+1} added per stage and
+  D_u on the control diagonal; xb_dense_vjp: the dense KKT solve (dense_vjp) with D added to L_zz.  No control is held by bit-equality; stages k < n_pin are held.
 
 Inputs: oracle.synth(20250213, 0, B, N, 0.002) with the x0 velocities clipped (XB of test_gpu_bounded_shapes.py),
 WEIGHTS_CFG / W_EXO, V* from oracle.solve_batch(x_lb=, x_ub=) with the exact Hessian at tol_grad 1e-11, tol_defect 1e-12.
@@ -31,26 +31,22 @@ Cases: 2-link (N, B) = (1, 5) (2, 3) (3, 9) (17, 9) (33, 9) under `box` (|qdot| 
    the finite difference's own error is a comparable term).
 
 Measured values (this module's prints) are recorded beside the constants they bound."""
-import math
-
 import numpy as np
 import pytest
 
 import oracle_lib as oracle
 from conftest import WEIGHTS_CFG
+from sens_reference import (CAP_DEFAULT, OUT, _residuals, _weight_sums, barrier_terms, mu_f, xb_dense_gains,
+                            stage_data, xb_dense_vjp, xb_stage_data)
 from test_gpu_bounded_shapes import XB
-from test_gpu_feedback_gains import stage_data
-from test_solve_vjp_reference import _residuals, _weight_sums
 
 H = 0.002
 SEED = 20250213
 W_2L = np.array(WEIGHTS_CFG)
 W_EXO = np.array([10.0] * 4 + [1.0] * 4 + [1.0] * 4 + [0.01] * 4)
-OUT = ("x0_bar", "u_prev_bar", "traj_bar", "weights_bar", "adj_V")
 NAME = {oracle.TWO_LINK: "two_link_arm", oracle.EXO: "exo_arm"}
 WEIGHTS = {oracle.TWO_LINK: W_2L, oracle.EXO: W_EXO}
 CAP_PIN = 1e6
-CAP_DEFAULT = 1e12
 # (model, pattern, N, B)
 CASES = [(oracle.TWO_LINK, "box", 1, 5), (oracle.TWO_LINK, "box", 2, 3), (oracle.TWO_LINK, "box", 3, 9),
          (oracle.TWO_LINK, "box", 17, 9), (oracle.TWO_LINK, "box", 33, 9), (oracle.TWO_LINK, "mixed+u", 17, 9),
@@ -83,14 +79,6 @@ CENTRAL_PATH = 0.574
 FD = 5.39e-7
 
 
-def mu_f():
-    """the barrier value the monotone schedule of csrc/sqp_wave.h reaches first with 2 mu <= 1e-8"""
-    mu, tol = 0.1, 1e-8
-    while 2.0 * mu > tol:
-        mu = max(tol / 20.0, min(0.2 * mu, math.pow(mu, 1.5)))
-    return mu
-
-
 def _id(case):
     return "-".join([NAME[case[0]]] + [str(v) for v in case[1:]])
 
@@ -100,49 +88,6 @@ def arr(v):
 
 
 # ---------------------------------------------------------------- the definition
-def barrier_terms(model, N, V, xl, xu, ul, uu, n_pin, mu, cap):
-    """beta(x_{k+1}) [N, nx], D(x_{k+1}) [N, nx], D(u_k) [N, nu] (0 for k < n_pin), the uncapped D of every bounded
-    entry and the smallest slack; a bound that is None or |b| >= 1e19 is infinite"""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    X = np.stack([V[(k + 1) * K:(k + 1) * K + nx] for k in range(N)])
-    U = V[:-nx].reshape(N, K)[:, nx:]
-
-    def side(b, n, sign):
-        b = np.full(n, sign * np.inf) if b is None else np.asarray(b, dtype=np.float64).copy()
-        b[np.abs(b) >= 1e19] = sign * np.inf
-        return b
-
-    def terms(Y, lo, hi):
-        sl, su = Y - lo[None, :], hi[None, :] - Y
-        with np.errstate(divide="ignore"):
-            beta = 2 * mu * (1 / su - 1 / sl)
-            D = 2 * mu * (1 / sl ** 2 + 1 / su ** 2)
-        return beta, D, np.minimum(sl, su)
-
-    bx, Dx, sx = terms(X, side(xl, nx, -1), side(xu, nx, 1))
-    _, Du, su = terms(U, side(ul, nu, -1), side(uu, nu, 1))
-    Du[:n_pin] = 0.0
-    su[:n_pin] = np.inf
-    raw = np.concatenate([Dx[np.isfinite(sx)], Du[np.isfinite(su)]])
-    return bx, np.minimum(Dx, cap), np.minimum(Du, cap), raw, min(sx.min(), su.min())
-
-
-def xb_stage_data(model, N, h, V, up, tr, w, exact, bx):
-    """A_k, B_k and the stage blocks of stage_data with beta(x_{k+1}) = bx[k] in the multipliers"""
-    nx, nu = oracle.DIMS[model]
-    A, B, blocks = stage_data(model, N, h, V, up, tr, w, False)
-    if exact:
-        Q = w[:nx]
-        e = _residuals(model, N, h, V, tr)
-        lam = np.zeros((N, nx))
-        lam[N - 1] = bx[N - 1]
-        for k in range(N - 2, -1, -1):
-            lam[k] = A[k + 1].T @ (2 * Q * e[k + 1] + lam[k + 1]) + bx[k]
-        blocks = oracle.nlp_hess(N, h, V, up, tr, w, 1.0, lam, model=model)
-    return A, B, blocks
-
-
 def xb_recursion(model, N, h, V, up, tr, w, Vbar, exact, xl, xu, ul=None, uu=None, n_pin=0, mu=None, cap=CAP_DEFAULT,
                  barrier=True):
     """the recursion of the definition, one instance: G [N, nu, K] and the VJP outputs for Vbar (None: zeros);
@@ -192,134 +137,6 @@ def xb_recursion(model, N, h, V, up, tr, w, Vbar, exact, xl, xu, ul=None, uu=Non
     e = _residuals(model, N, h, V, tr)
     return dict(G=G, x0_bar=p[:nx], u_prev_bar=p[nx:], traj_bar=2 * Q[None, :] * ax_next,
                 weights_bar=_weight_sums(model, N, V, up, e, a, ax_next), adj_V=a)
-
-
-# ---------------------------------------------------------------- the dense reference
-def refined_solve(A, b):
-    """A^-1 b by LU in double with iterative refinement on extended-precision residuals (A and b may be extended
-    themselves); returned in double.  With D up to the cap on the diagonal the plain solve's own error (measured
-    1.6e-10 on weights_bar at N = 33, cap 1e6, where the recursion agrees with the refined solve to 3e-14) would
-    otherwise be charged to the code under test."""
-    LD = np.longdouble
-    A64, Al, bl = A.astype(np.float64), A.astype(LD), b.astype(LD)
-    x = np.linalg.solve(A64, bl.astype(np.float64)).astype(LD)
-    for _ in range(4):
-        x = x + np.linalg.solve(A64, (bl - Al @ x).astype(np.float64)).astype(LD)
-    return x.astype(np.float64)
-
-
-def xb_dense_gains(model, N, h, V, up, tr, w, exact, xl, xu, ul=None, uu=None, n_pin=0, mu=None, cap=CAP_DEFAULT,
-                   stages=None):
-    """G_k [nu, K] for k in stages (default all N) from the dense tail problems, one instance.  The tail systems of
-    tests/test_gpu_feedback_gains.py::tail_system with the barrier added, assembled in extended precision (the double
-    assembly of sums with D = 1e6 beside entries of order 1 carries 7e-11 at exo N = 7, three times the recursion's
-    own error): H_UU of the tail from stage k is the trailing block of stage 0's, since no state depends on a later
-    control, and H_Up's state columns follow backward from T_k = Yu_k^T S_k[:, x] + (T_{k+1} + Su_{k+1}^T D_k) A_k."""
-    LD = np.longdouble
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    w = np.asarray(w, dtype=np.float64)
-    R = w[nx:nx + nu]
-    mu = mu_f() if mu is None else mu
-    bx, Dx, Du, _, _ = barrier_terms(model, N, V, xl, xu, ul, uu, n_pin, mu, cap)
-    A, B, blocks = xb_stage_data(model, N, h, V, up, tr, w, exact, bx)
-    A, B, blocks = [a.astype(LD) for a in A], [b.astype(LD) for b in B], blocks.astype(LD)
-    Dx, Du = Dx.astype(LD), Du.astype(LD)
-    n = N * nu
-    Su, HUU = np.zeros((nx, n), LD), np.zeros((n, n), LD)
-    Yus, Sus = [], []
-    for j in range(N):
-        cols = j * nu + np.arange(nu)
-        Yu = np.zeros((K, n), LD)    # (dx_j, du_j) as functions of dU
-        Yu[:nx] = Su
-        Yu[nx + np.arange(nu), cols] = 1.0
-        HUU += Yu.T @ (blocks[j] @ Yu)
-        HUU[cols, cols] += Du[j]
-        Su = A[j] @ Su + B[j] @ Yu[nx:]
-        HUU += Su.T @ (Dx[j][:, None] * Su)      # the barrier of x_{j+1}
-        Yus.append(Yu)
-        Sus.append(Su)
-    for j in range(1, N):
-        for c in range(nu):
-            HUU[j * nu + c, (j - 1) * nu + c] -= 2 * R[c]
-            HUU[(j - 1) * nu + c, j * nu + c] -= 2 * R[c]
-    HUU = (HUU + HUU.T) / 2
-    T = np.zeros((n, nx), LD)
-    Ts = [None] * N
-    for k in range(N - 1, -1, -1):
-        T = Yus[k].T @ blocks[k][:, :nx] + (Sus[k].T * Dx[k][None, :] + T) @ A[k]
-        Ts[k] = T
-    stages = range(N) if stages is None else stages
-    out = np.zeros((len(stages), nu, K))
-    for i, k in enumerate(stages):
-        r0 = k * nu
-        HUp = np.zeros((n - r0, K), LD)
-        HUp[:, :nx] = Ts[k][r0:]
-        for c in range(nu):
-            HUp[c, nx + c] -= 2 * R[c]
-        free = np.repeat(np.arange(k, N) >= n_pin, nu)
-        dU = np.zeros((n - r0, K))
-        if free.any():
-            dU[free] = -refined_solve(HUU[r0:, r0:][np.ix_(free, free)], HUp[free])
-        out[i] = dU[:nu]
-    return out
-
-
-def xb_dense_vjp(model, N, h, V, up, tr, w, Vbar, exact, xl, xu, ul=None, uu=None, n_pin=0, mu=None, cap=CAP_DEFAULT):
-    """every VJP output for one instance from one dense KKT solve with D on the diagonal of L_zz"""
-    nx, nu = oracle.DIMS[model]
-    K = nx + nu
-    NV = V.size
-    w = np.asarray(w, dtype=np.float64)
-    Q, R = w[:nx], w[nx:nx + nu]
-    mu = mu_f() if mu is None else mu
-    bx, Dx, Du, _, _ = barrier_terms(model, N, V, xl, xu, ul, uu, n_pin, mu, cap)
-    A, B, blocks = xb_stage_data(model, N, h, V, up, tr, w, exact, bx)
-    Hm = np.zeros((NV, NV))
-    Gz = np.zeros((N * nx, NV))
-    for k in range(N):
-        Hm[k * K:(k + 1) * K, k * K:(k + 1) * K] += blocks[k]
-        iu, ix = k * K + nx + np.arange(nu), (k + 1) * K + np.arange(nx)
-        Hm[iu, iu] += Du[k]
-        Hm[ix, ix] += Dx[k]
-        Gz[k * nx:(k + 1) * nx, k * K:(k + 1) * K] = np.hstack([A[k], B[k]])
-        Gz[k * nx + np.arange(nx), ix] = -1.0
-        if k >= 1:
-            j = iu - K
-            Hm[iu, j] -= 2 * R
-            Hm[j, iu] -= 2 * R
-    free = np.ones(NV, bool)
-    free[:nx] = False
-    for k in range(n_pin):
-        free[k * K + nx:(k + 1) * K] = False
-    nf, ng = int(free.sum()), N * nx
-    KKT = np.zeros((nf + ng, nf + ng))
-    KKT[:nf, :nf] = Hm[np.ix_(free, free)]
-    KKT[nf:, :nf] = Gz[:, free]
-    KKT[:nf, nf:] = Gz[:, free].T
-    sol = refined_solve(KKT, np.concatenate([Vbar[free], np.zeros(ng)]))
-    a = np.zeros(NV)
-    a[free] = sol[:nf]
-    b = sol[nf:]
-    x0_bar = Vbar[:nx] - Hm[:, :nx].T @ a - Gz[:, :nx].T @ b
-    ax_next = np.stack([np.hstack([A[k], B[k]]) @ a[k * K:(k + 1) * K] for k in range(N)])
-    e = _residuals(model, N, h, V, tr)
-    return dict(x0_bar=x0_bar, u_prev_bar=2 * R * a[nx:K], traj_bar=2 * Q[None, :] * ax_next,
-                weights_bar=_weight_sums(model, N, V, up, e, a, ax_next), adj_V=a)
-
-
-def xb_dense_gains_batch(model, N, h, V, up, tr, w, exact, xl, xu, ul=None, uu=None, **kw):
-    """xb_dense_gains for every instance [B, n, nu, K]; ul / uu [nu] shared or [B, nu]"""
-    row = lambda a, b: None if a is None else (np.asarray(a, dtype=np.float64)[b] if np.ndim(a) == 2 else a)  # noqa: E731
-    return np.stack([xb_dense_gains(model, N, h, V[b], up[b], tr[b], w, exact, xl, xu, row(ul, b), row(uu, b), **kw)
-                     for b in range(V.shape[0])])
-
-
-def xb_dense_vjp_batch(model, N, h, V, up, tr, w, Vbar, exact, xl, xu, ul=None, uu=None, **kw):
-    row = lambda a, b: None if a is None else (np.asarray(a, dtype=np.float64)[b] if np.ndim(a) == 2 else a)  # noqa: E731
-    rows = [xb_dense_vjp(model, N, h, V[b], up[b], tr[b], w, Vbar[b], exact, xl, xu, row(ul, b), row(uu, b), **kw)
-            for b in range(V.shape[0])]
-    return {k: np.stack([r[k] for r in rows]) for k in OUT}
 
 
 # ---------------------------------------------------------------- the cases
