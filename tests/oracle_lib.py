@@ -130,6 +130,17 @@ def use_user_model(name) -> int:
     return USER
 
 
+def active_user_model(name=None) -> UserModelHost:
+    """The host build use_user_model registered last (the oracle has one USER slot).  With `name`: raises unless that
+    is the registered model, so that a registration another caller replaced cannot serve this one's Jacobians."""
+    m = _user.get("active")
+    if m is None:
+        raise RuntimeError("no generated model is registered (use_user_model)")
+    if name is not None and m.name != name:
+        raise RuntimeError(f"the oracle's USER model is {m.name}, not {name}: call use_user_model({name!r}) first")
+    return m
+
+
 def c64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 

@@ -6,7 +6,9 @@ state-bounded handle), shared by their CPU and GPU test mo
 * dense_vjp / dense_vjp_batch: the dense KKT solve of tests/test_solve_vjp_reference.py's docstring; fd_delta is the
   step of the central differences taken against it.
 * xb_dense_gains / xb_dense_vjp and their batches: the same two with the barrier's terms (barrier_terms,
-  xb_stage_data), assembled or refined in extended precision; tests/test_xb_sensitivity_reference.py's docstring."""
+  xb_stage_data), assembled or refined in extended precision; tests/test_xb_sensitivity_reference.py's docstring.
+* model = oracle.USER: a generated model (use_user_model of this module registers it; _jac reads the host build of its
+  generated header and raises when the oracle's one USER slot holds another model by then)."""
 import math
 
 import numpy as np
@@ -18,7 +20,21 @@ CAP_DEFAULT = 1e12
 
 
 # ---------------------------------------------------------------- feedback gains: the dense tail sensitivity
+_user_name = None   # the generated model use_user_model of this module registered last
+
+
+def use_user_model(name):
+    """Register generated model `name` as the oracle's USER model for the references of this module; returns
+    oracle.USER.  The oracle has one USER slot: call this before every reference or oracle solve of that model."""
+    global _user_name
+    _user_name = name
+    return oracle.use_user_model(name)
+
+
 def _jac(model, x, u):
+    if model == oracle.USER:   # raises if the slot was never filled through this module or holds another model since
+        assert _user_name is not None, "sens_reference.use_user_model(name) comes first"
+        return oracle.active_user_model(_user_name).jac(x, u)
     return (oracle.exo_jac if model == oracle.EXO else oracle.two_link_jac)(x, u)
 
 

@@ -103,19 +103,26 @@ def test_nlp_derivs_generated_model(mmpc_mod, oracle):
         np.testing.assert_allclose(JB[b].cpu().numpy(), bn, rtol=1e-12, atol=1e-14)
 
 
-@pytest.mark.parametrize("model", ["two_link_arm", "cart_pole", "exo_arm"])
+SX_DIMS = {"cart_pole": (4, 1), "unicycle": (4, 2), "motor_pendulum": (3, 1), "mass_chain": (12, 4)}   # NQ = 2, 0, 1, 6
+
+
+@pytest.mark.parametrize("model", ["two_link_arm", "cart_pole", "exo_arm", "unicycle", "motor_pendulum", "mass_chain"])
 def test_nlp_hess(model, mmpc_mod, oracle, tmp_path):
     """mmpc_nlp_hess_batch (nlp_hess_l, ModelGenerator.cpp:238): the (x_k, u_k) stage blocks of the Hessian of
     lam_f J + lam_g^T g against the oracle's (its own hyper-dual second derivatives for the 2-link arm; the host build
-    of the generated header, itself pinned to sympy, for cart-pole; round 4: the exo's analytic Hessian, oracle_exo_hess,
-    itself checked against differences of the analytic Jacobian) at 1e-12 relative; symmetric."""
+    of the generated header, itself pinned to sympy, for the generated models -- second order, first order (NQ = 0),
+    mixed (NQ = 1) and the widest (nx + nu = 16); round 4: the exo's analytic Hessian, oracle_exo_hess, itself checked
+    against differences of the analytic Jacobian) at 1e-12 relative; symmetric."""
     B, lam_f = 24, 0.7
-    if model == "cart_pole":
-        path = os.path.join(ROOT, "mahi-mpc_amd", "lib", "user", "cart_pole.json")
-        if not os.path.exists(path):
-            pytest.skip("cart_pole not generated")
-        s = mmpc_mod.Solver(path)
-        om = oracle.use_user_model("cart_pole")
+    if model in SX_DIMS:
+        so = os.path.join(ROOT, "mahi-mpc_amd", "lib", "user", f"{model}.so")
+        if not os.path.exists(so):
+            pytest.skip(f"{model} not generated")
+        nx, nu = SX_DIMS[model]
+        s = mmpc_mod.Solver(mmpc_mod.write_model_json(str(tmp_path / f"{model}.json"), model, nx, nu, 10000, 20,
+                                                      dll_filepath=so, model=model))
+        assert s.info.model_id == mmpc_mod.MODEL_USER
+        om = oracle.use_user_model(model)
     else:
         nx, nu = (8, 4) if model == "exo_arm" else (4, 2)
         s = mmpc_mod.Solver(mmpc_mod.write_model_json(str(tmp_path / "m.json"), "m", nx, nu, 2000, 12, model=model))
