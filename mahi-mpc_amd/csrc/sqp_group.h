@@ -170,19 +170,40 @@ struct GroupWork {
     double* ws;
 };
 
+// Reductions over one 16-lane row (= one instance group): a butterfly of DPP row rotations by 8, 4, 2, 1 (two
+// v_mov_b32_dpp row_ror and the FP64 operation per step; no LDS access -- the __shfl_xor butterfly they replace was two
+// ds_bpermute_b32 and an LDS round trip per step).  Values: after the step with offset o every lane's value has period
+// 2 o over the row, so the lane o places round holds what lane i ^ o holds, and each lane forms op(own, partner) with
+// the xor butterfly's operands in the xor butterfly's order: the results are its results bit for bit.
+// Every call is group-uniform: all 16 lanes of the row are active (bound_ctrl would hand an inactive lane's partner a
+// zero).  Checked at every call site of sqp_group.h and gain_sweep.h: each sits under conditions on template flags,
+// launch parameters, the iteration count and values that are themselves group reductions or computed redundantly on
+// every lane (evalA / fwd_ready, resolve, fact_ok, the line search's tests), never under a lane or stage test; groups
+// of one wave may diverge from each other, which a row operation does not see.
+template <int O>
+__device__ __forceinline__ double row_ror(double v) {
+    static_assert(O >= 1 && O < 16, "row rotation");
+    return __builtin_amdgcn_update_dpp(v, v, 0x120 + O, 0xf, 0xf, true);
+}
 __device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    v += row_ror<8>(v);
+    v += row_ror<4>(v);
+    v += row_ror<2>(v);
+    v += row_ror<1>(v);
     return v;
 }
 __device__ __forceinline__ double group_min(double v) {
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    v = fmin(v, row_ror<8>(v));
+    v = fmin(v, row_ror<4>(v));
+    v = fmin(v, row_ror<2>(v));
+    v = fmin(v, row_ror<1>(v));
     return v;
 }
 __device__ __forceinline__ double group_max(double v) {
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    v = fmax(v, row_ror<8>(v));
+    v = fmax(v, row_ror<4>(v));
+    v = fmax(v, row_ror<2>(v));
+    v = fmax(v, row_ror<1>(v));
     return v;
 }
 __device__ __forceinline__ double group_bcast(double v, int base) { return __shfl(v, base); }
