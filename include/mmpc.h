@@ -472,6 +472,65 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
                               double* x0_bar, double* u_prev_bar, double* traj_bar, double* weights_bar, double* adj_V,
                               int32_t* vjp_status);
 
+/* ---- forward sensitivity of the solve: the first-order plan update (solve JVP; additive to ABI 6) ----
+ * The forward-mode product dV = (d V* / d theta) d theta for theta = (x0, u_prev, traj, weights): when the measured
+ * state, the applied control and the targets have all moved a little since the plan was computed, V* + dV is the plan
+ * updated to first order (the feedback step of real-time iteration), and the best warm start of the next solve.
+ *
+ * Definition.  Notation of the gain and VJP comments above: A_k, B_k, J_k = [A_k | B_k], e_k = F(x_k, u_k) - r_k,
+ * C_k, S_k (+ W_k), nu_k, lam_k, the held mask (bit-equal to a finite bound, or k < n_pin), M_uu, M_us, M_ss, G_k.
+ * Tangents: dx0 [nx], du_prev [nu], dtraj [N][nx], dweights = (dQ | dR | dRm) [nx+2nu]; a missing tangent is zero.
+ * Right-hand side, per stage on y_k = (x_k, u_k):
+ *   rho_k = J_k^T (2 Q o dtraj_k - 2 dQ o e_k),
+ *   plus on the u rows  - 2 dR o ((u_k - u_{k-1}) - (u_{k+1} - u_k)) - 2 dRm o u_k,
+ *   with u_{-1} = u_prev and the (u_{k+1} - u_k) term absent at k = N-1;
+ * rho is -d(grad_V L)/d theta d theta for traj and the weights; rho on x_N is 0.
+ * Recursion: backward over k = N-1..0 from P_N = 0, p_N = 0, with P_k, M_*, G_k exactly as in the gains (with the
+ * sensitivity barrier's terms when it is on):  q = C_k^T p_{k+1} + rho_k;  q_u of a held control is 0;
+ * kff_k = M_uu^-1 q_u;  p_k = (q_x; 0) + G_k^T q_u.  Forward from s_0 = (dx0, du_prev):  du_k = G_k s_k + kff_k,
+ * dx_{k+1} = A_k dx_k + B_k du_k,  s_{k+1} = (dx_{k+1}, du_k).  dV = (dx0, du_0, dx_1, .., dx_N).
+ * Held controls have du = 0: the active set and the pins are assumed unchanged (the VJP's "V_bar on held controls is
+ * ignored").  V need not be a solution: the result is that of the quadratic model at the V given.  Per instance:
+ *   jvp_status 0   as asked
+ *              1   Gauss-Newton fallback: a pivot <= 0 or non-finite under EXACT redoes the whole instance, both sweeps,
+ *                  with Gauss-Newton
+ *              2   failed (non-finite input, or not positive definite even with Gauss-Newton): every output row of the
+ *                  instance is written as 0; neighbours in the batch are untouched
+ *
+ * Arguments.  V, u_prev, traj, weights / weights_stride, u_lb, u_ub, bounds_stride, n_pin: as for
+ * mmpc_solve_vjp_batch, validation included.
+ *   dx0 [B][nx]   du_prev [B][nu]   dtraj [B][N][nx]   dweights [B][nx+2nu], always per instance.
+ *                Each may be NULL (zero); all four NULL: MMPC_ERR_INVALID_ARG.
+ *   hessian      enum mmpc_hessian.  AUTO means EXACT wherever the model has second derivatives; GAUSS_NEWTON is
+ *                available and is NOT the true derivative.
+ *   dV           [B][NV] or NULL      du0  [B][nu] or NULL: du_0, the correction of the control about to be applied, for
+ *                a state error and a target change together.  Both NULL: MMPC_ERR_INVALID_ARG.  With dV given, du0 is
+ *                bit for bit the u_0 entries of dV.
+ *   jvp_status   [B] or NULL.
+ *   workspace    DEVICE memory of mmpc_solve_jvp_workspace_bytes(h, B) bytes for the records G_k | kff_k: the layout
+ *                and the size of mmpc_solve_vjp_workspace_bytes.
+ * Forward-free mode: when dV is NULL no record is stored, no forward sweep runs and workspace may be NULL; du0 is bit
+ * for bit the full call's wherever both report status 0 or 1.  Otherwise a workspace that is NULL or smaller than the
+ * query: MMPC_ERR_INVALID_ARG naming `workspace` / `workspace_bytes`.
+ * Refused with MMPC_ERR_UNSUPPORTED: a linear-mode model; a handle with any finite state bound whose sensitivity
+ * barrier is off.  The remaining rules, codes and argument names are the VJP's.  Everything is checked from the
+ * arguments alone before any device call; B = 0 is a no-op success.
+ * mmpc_solve_jvp_batch takes DEVICE pointers and is one stream-ordered launch on `stream` that never synchronises and
+ * never allocates (the handle's workspace is not used; mmpc_reserve_workspace's sizes are unchanged), so it can be
+ * captured in a hipGraph.  mmpc_solve_jvp_batch_host takes host pointers, stages them, brings its own workspace and is
+ * synchronous.  Multi-device and RCCL entries, a 16-lane kernel, tangents of the bounds and the pins: out of scope. */
+int mmpc_solve_jvp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes);
+int mmpc_solve_jvp_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                         const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                         int64_t bounds_stride, int32_t n_pin, const double* dx0, const double* du_prev,
+                         const double* dtraj, const double* dweights, int32_t hessian, double* dV, double* du0,
+                         int32_t* jvp_status, void* workspace, uint64_t workspace_bytes, void* stream);
+int mmpc_solve_jvp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, const double* dx0, const double* du_prev,
+                              const double* dtraj, const double* dweights, int32_t hessian, double* dV, double* du0,
+                              int32_t* jvp_status);
+
 /* ---- feedback gains and solve VJP of a state-bounded handle: the sensitivity barrier (additive to ABI 6) ----
  * A state-bounded solve is an interior-point solve: the V it returns lies strictly inside every bound, near the
  * central path of its last barrier value.  Its sensitivity is the recursion of the two definitions above with the
@@ -509,7 +568,8 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
  * mmpc_solve_vjp_batch[_host] accept the handle with the same signatures and launch rules (no allocation, no
  * synchronisation, hipGraph capture; mmpc_solve_vjp_workspace_bytes and mmpc_reserve_workspace unchanged); the
  * 16-lane gain kernel's stage records grow by 2 nx + nu doubles, and its availability and the AUTO rule are evaluated
- * with that size.  Gradients with respect to the bounds, a per-instance mu_s: out of scope. */
+ * with that size.  mmpc_solve_jvp_batch[_host] accept it on the same terms: its right-hand side does not depend on
+ * the barrier.  Gradients with respect to the bounds, a per-instance mu_s: out of scope. */
 int mmpc_sensitivity_barrier_default(double* mu, double* sigma_cap);
 int mmpc_set_sensitivity_barrier(mmpc_handle* h, double mu, double sigma_cap);
 int mmpc_get_sensitivity_barrier(const mmpc_handle* h, double* mu, double* sigma_cap);

@@ -25,6 +25,7 @@
 #include "../../include/mmpc.h"
 #include "json_lite.h"
 #include "adjoint_sweep.h"
+#include "tangent_sweep.h"
 #include "gain_sweep.h"
 #include "group_launch.h"
 #include "lane_launch.h"
@@ -1598,6 +1599,61 @@ int launch_vjp(mmpc_handle* h, const VjpArgs& a, bool exact, const XbTail& xb) {
     });
 }
 
+// ---- forward-mode product of the solve (mmpc_solve_jvp_batch; tangent_sweep.h) ----
+struct JvpArgs : SensArgs {
+    const double *dx0 = nullptr, *du_prev = nullptr, *dtraj = nullptr, *dweights = nullptr;
+    double *dV = nullptr, *du0 = nullptr;
+    void* workspace = nullptr;
+    uint64_t workspace_bytes = 0;
+    bool forward() const { return dV != nullptr; }   // else forward-free: no record, no workspace
+};
+// The one check of a JVP call's arguments: check_sens_args with the rules of the tangents, the outputs and the
+// workspace (the host entry brings its own workspace and passes check_workspace = false).  The record is the VJP's,
+// and so is the workspace's size.
+int check_jvp_args(mmpc_handle* h, const JvpArgs& a, bool check_workspace, bool* exact, XbTail* xb) {
+    const int rc = check_sens_args(h, a, "the solve JVP is", exact, xb, [&](SensRule at) -> int {
+        if (at != SensRule::kAfterInputs) return MMPC_OK;
+        if (!a.dx0 && !a.du_prev && !a.dtraj && !a.dweights)
+            return fail(MMPC_ERR_INVALID_ARG, "dx0, du_prev, dtraj and dweights are all NULL: no tangent");
+        if (!a.dV && !a.du0) return fail(MMPC_ERR_INVALID_ARG, "dV and du0 are both NULL: no output");
+        return MMPC_OK;
+    });
+    if (rc || a.B == 0) return rc;
+    if (check_workspace && a.forward()) {
+        const uint64_t need = vjp_workspace_bytes(h->info, a.B);
+        if (!a.workspace)
+            return fail(MMPC_ERR_INVALID_ARG, "workspace is NULL: dV needs " + std::to_string(need) +
+                                                  " bytes (mmpc_solve_jvp_workspace_bytes)");
+        if (a.workspace_bytes < need)
+            return fail(MMPC_ERR_INVALID_ARG, "workspace_bytes is " + std::to_string(a.workspace_bytes) + ", needs " +
+                                                  std::to_string(need) + " (mmpc_solve_jvp_workspace_bytes)");
+    }
+    return MMPC_OK;
+}
+// a JVP call whose arguments check_jvp_args has passed, B > 0, device pointers, on the current device: one launch,
+// stream-ordered, no allocation, no synchronisation
+int launch_jvp(mmpc_handle* h, const JvpArgs& a, bool exact, const XbTail& xb) {
+    TangentXbParams p{};
+    fill_sens_params(h, a, xb, p);
+    p.dx0 = a.dx0;
+    p.du_prev = a.du_prev;
+    p.dtraj = a.dtraj;
+    p.dweights = a.dweights;
+    p.dV = a.dV;
+    p.du0 = a.du0;
+    p.status = a.status;
+    p.ws = a.forward() ? static_cast<double*>(a.workspace) : nullptr;
+    return with_model(h->info.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        return with_sens_variant<M>(exact, a.u_lb || a.u_ub, xb.mu > 0.0, [&](auto ex, auto bd, auto x) -> int {
+            tangent_lane_kernel<M, decltype(ex)::value, decltype(bd)::value, decltype(x)::value>
+                <<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
+            MMPC_HIP(hipGetLastError());
+            return MMPC_OK;
+        });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -2032,6 +2088,79 @@ int mmpc_solve_vjp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
         MMPC_HIP(back(weights_bar, off_wb, B * nw));
         MMPC_HIP(back(adj_V, off_a, B * NV));
         if (vjp_status) MMPC_HIP(hipMemcpyAsync(vjp_status, a.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MMPC_HIP(hipStreamSynchronize(s));
+        return MMPC_OK;
+    });
+}
+
+int mmpc_solve_jvp_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes) {
+    if (!h || !bytes || B < 0) return fail(MMPC_ERR_INVALID_ARG, "null argument or B < 0");
+    *bytes = vjp_workspace_bytes(h->info, B);
+    return MMPC_OK;
+}
+
+int mmpc_solve_jvp_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                         const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                         int64_t bounds_stride, int32_t n_pin, const double* dx0, const double* du_prev,
+                         const double* dtraj, const double* dweights, int32_t hessian, double* dV, double* du0,
+                         int32_t* jvp_status, void* workspace, uint64_t workspace_bytes, void* stream) {
+    JvpArgs a;
+    static_cast<SensArgs&>(a) = SensArgs{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin,
+                                         hessian, jvp_status, reinterpret_cast<hipStream_t>(stream)};
+    a.dx0 = dx0, a.du_prev = du_prev, a.dtraj = dtraj, a.dweights = dweights;
+    a.dV = dV, a.du0 = du0, a.workspace = workspace, a.workspace_bytes = workspace_bytes;
+    bool exact = false;
+    XbTail xb;
+    if (int rc = check_jvp_args(h, a, true, &exact, &xb)) return rc;
+    if (B == 0) return MMPC_OK;
+    return on_handle_device(h, [&] { return launch_jvp(h, a, exact, xb); });
+}
+
+int mmpc_solve_jvp_batch_host(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                              const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                              int64_t bounds_stride, int32_t n_pin, const double* dx0, const double* du_prev,
+                              const double* dtraj, const double* dweights, int32_t hessian, double* dV, double* du0,
+                              int32_t* jvp_status) {
+    JvpArgs a;
+    static_cast<SensArgs&>(a) =
+        SensArgs{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian};
+    a.dx0 = dx0, a.du_prev = du_prev, a.dtraj = dtraj, a.dweights = dweights;
+    a.dV = dV, a.du0 = du0;
+    bool exact = false;
+    XbTail xb;
+    if (int rc = check_jvp_args(h, a, false, &exact, &xb)) return rc;   // before the strides size a copy
+    if (B == 0) return MMPC_OK;
+    std::lock_guard<std::mutex> lk(h->host_mu);
+    return on_handle_device(h, [&]() -> int {
+        const mmpc_model_info& mi = h->info;
+        const size_t nx = mi.num_x, nu = mi.num_u, N = mi.num_shooting_nodes, NV = mi.num_v, nw = nx + 2 * nu;
+        const size_t nWs = a.forward() ? vjp_workspace_bytes(mi, B) / sizeof(double) : 0;
+        // own regions, after u_ub: dx0 | du_prev | dtraj | dweights | dV | du0 | the records
+        double* d;
+        size_t off_none, off_dx0;
+        const size_t n_own = B * nx + B * nu + B * N * nx + B * nw + B * NV + B * nu + nWs;
+        if (int rc = stage_sens_inputs(h, a, 0, n_own, &d, &off_none, &off_dx0)) return rc;
+        const size_t off_dup = off_dx0 + B * nx, off_dtr = off_dup + B * nu, off_dw = off_dtr + B * N * nx;
+        const size_t off_dV = off_dw + B * nw, off_du0 = off_dV + B * NV, off_ws = off_du0 + B * nu;
+        hipStream_t s = a.stream;
+        const auto in = [&](const double*& src, size_t off, size_t n) {
+            if (!src) return hipSuccess;
+            const hipError_t e = hipMemcpyAsync(d + off, src, n * sizeof(double), hipMemcpyHostToDevice, s);
+            src = d + off;
+            return e;
+        };
+        MMPC_HIP(in(a.dx0, off_dx0, B * nx));
+        MMPC_HIP(in(a.du_prev, off_dup, B * nu));
+        MMPC_HIP(in(a.dtraj, off_dtr, B * N * nx));
+        MMPC_HIP(in(a.dweights, off_dw, B * nw));
+        a.dV = dV ? d + off_dV : nullptr;
+        a.du0 = du0 ? d + off_du0 : nullptr;
+        a.workspace = nWs ? d + off_ws : nullptr;
+        a.workspace_bytes = nWs * sizeof(double);
+        if (int rc = launch_jvp(h, a, exact, xb)) return rc;
+        if (dV) MMPC_HIP(hipMemcpyAsync(dV, d + off_dV, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (du0) MMPC_HIP(hipMemcpyAsync(du0, d + off_du0, B * nu * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (jvp_status) MMPC_HIP(hipMemcpyAsync(jvp_status, a.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         MMPC_HIP(hipStreamSynchronize(s));
         return MMPC_OK;
     });

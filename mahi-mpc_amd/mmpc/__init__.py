@@ -50,6 +50,8 @@ GAIN_KERNEL_AUTO, GAIN_KERNEL_LANE, GAIN_KERNEL_GROUP = 0, 1, 2
 GAIN_OK, GAIN_GAUSS_NEWTON_FALLBACK, GAIN_FAILED = 0, 1, 2
 # per-instance status of the solve VJP (mmpc_solve_vjp_batch): the same three values
 VJP_OK, VJP_GAUSS_NEWTON_FALLBACK, VJP_FAILED = 0, 1, 2
+# and of the solve JVP (mmpc_solve_jvp_batch)
+JVP_OK, JVP_GAUSS_NEWTON_FALLBACK, JVP_FAILED = 0, 1, 2
 MODEL_TWO_LINK_ARM, MODEL_EXO_ARM, MODEL_USER = 0, 1, 2
 USER_LIB_DIR = os.path.join(ROOT, "lib", "user")
 BUILTIN_MODELS = ("two_link_arm", "double_pendulum", "exo_arm", "exo")  # "mmpc_model" names libmmpc.so serves   # models generated from SX by ModelGenerator (make -C host user)
@@ -137,6 +139,13 @@ def lib(path: str | None = None):
         L.mmpc_solve_vjp_batch.argtypes = _vjp + [_vp, C.c_uint64, _vp]
         L.mmpc_solve_vjp_batch_host.argtypes = _vjp
         L.mmpc_solve_vjp_workspace_bytes.argtypes = [_vp, C.c_int64, C.POINTER(C.c_uint64)]
+        # solve JVP: (V, u_prev, traj, weights), weights_stride, (u_lb, u_ub), bounds_stride, n_pin, (dx0, du_prev,
+        # dtraj, dweights), hessian, (dV, du0, jvp_status[, workspace, workspace_bytes, stream])
+        _jvp = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64, C.c_int32] + [_vp] * 4 + [C.c_int32]
+                + [_vp] * 3)
+        L.mmpc_solve_jvp_batch.argtypes = _jvp + [_vp, C.c_uint64, _vp]
+        L.mmpc_solve_jvp_batch_host.argtypes = _jvp
+        L.mmpc_solve_jvp_workspace_bytes.argtypes = [_vp, C.c_int64, C.POINTER(C.c_uint64)]
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -563,6 +572,67 @@ class Solver:
                                                       _ptr(out["x0_bar"]), _ptr(out["u_prev_bar"]),
                                                       _ptr(out["traj_bar"]), _ptr(out["weights_bar"]),
                                                       _ptr(out["adj_V"]), _ptr(out["vjp_status"])))
+        return out
+
+    def solve_jvp_workspace_bytes(self, B) -> int:
+        """Bytes of the record workspace a full solve_jvp of B instances needs (mmpc_solve_jvp_workspace_bytes)."""
+        n = C.c_uint64(0)
+        self._check(self._L.mmpc_solve_jvp_workspace_bytes(self._h, B, C.byref(n)))
+        return int(n.value)
+
+    def solve_jvp(self, B, V, u_prev, traj, weights, dx0=None, du_prev=None, dtraj=None, dweights=None, dV=None,
+                  du0=None, jvp_status=None, workspace=None, workspace_bytes=None, weights_stride=0, u_lb=None,
+                  u_ub=None, bounds_stride=0, n_pin=0, hessian=HESSIAN_AUTO, forward_free=False, stream=None):
+        """Forward-mode product of the solve at V (mmpc_solve_jvp_batch; device tensors, one stream-ordered launch):
+        dV = (d V* / d theta) d theta for the tangents dx0 [B, nx], du_prev [B, nu], dtraj [B, N, nx] and dweights
+        [B, nx + 2 nu] (None: zero; at least one is needed) -- V + dV is the plan updated to first order.  Returns a
+        dict with dV [B, NV], du0 [B, nu] (the u_0 entries of dV) and jvp_status [B] int32 (0 as asked, 1 Gauss-Newton
+        fallback, 2 failed: rows 0).  Outputs and the workspace are torch tensors on V's device unless given (tensors
+        or raw addresses, used as given; a raw workspace address needs workspace_bytes).  forward_free: only du0 and
+        jvp_status -- no forward sweep, no workspace; dV is then None."""
+        nx, nu, NV = self.nx, self.nu, self.NV
+        if forward_free and dV is not None:
+            raise ValueError("forward_free takes no dV")
+        out = dict(dV=dV, du0=du0, jvp_status=jvp_status)
+        shapes = dict(dV=(B, NV), du0=(B, nu), jvp_status=(B,))
+        want = [k for k in out if out[k] is None and not (forward_free and k == "dV")]
+        if want or (workspace is None and not forward_free):
+            import torch
+            for k in want:
+                out[k] = torch.empty(shapes[k], dtype=torch.int32 if k == "jvp_status" else torch.float64,
+                                     device=V.device)
+            if workspace is None and not forward_free:
+                workspace = torch.empty((max(self.solve_jvp_workspace_bytes(B), 8) // 8,), dtype=torch.float64,
+                                        device=V.device)
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else 0
+        self._check(self._L.mmpc_solve_jvp_batch(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                 weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                 int(n_pin), _ptr(dx0), _ptr(du_prev), _ptr(dtraj), _ptr(dweights),
+                                                 int(hessian), _ptr(out["dV"]), _ptr(out["du0"]),
+                                                 _ptr(out["jvp_status"]), _ptr(workspace), int(workspace_bytes),
+                                                 stream))
+        return out
+
+    def solve_jvp_host(self, V, u_prev, traj, weights, dx0=None, du_prev=None, dtraj=None, dweights=None, u_lb=None,
+                       u_ub=None, n_pin=0, hessian=HESSIAN_AUTO, forward_free=False):
+        """solve_jvp for numpy arrays, synchronous (mmpc_solve_jvp_batch_host; the library brings the workspace);
+        u_lb / u_ub [nu] shared or [B, nu] per instance.  Returns a dict of numpy arrays with solve_jvp's keys."""
+        nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
+        V = _f64(V, (-1, NV))
+        B = V.shape[0]
+        u_prev, traj, weights = _f64(u_prev, (B, nu)), _f64(traj, (B, N, nx)), _f64(weights)
+        opt = lambda t, shape: None if t is None else _f64(t, shape)  # noqa: E731
+        dx0, du_prev, dtraj = opt(dx0, (B, nx)), opt(du_prev, (B, nu)), opt(dtraj, (B, N, nx))
+        dweights = opt(dweights, (B, nx + 2 * nu))
+        ws = 0 if weights.ndim == 1 else weights.shape[-1]
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)
+        out = dict(dV=None if forward_free else np.zeros((B, NV)), du0=np.zeros((B, nu)),
+                   jvp_status=np.full(B, -1, np.int32))
+        self._check(self._L.mmpc_solve_jvp_batch_host(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights), ws,
+                                                      _ptr(lb), _ptr(ub), bs, int(n_pin), _ptr(dx0), _ptr(du_prev),
+                                                      _ptr(dtraj), _ptr(dweights), int(hessian), _ptr(out["dV"]),
+                                                      _ptr(out["du0"]), _ptr(out["jvp_status"])))
         return out
 
     def set_state_bounds(self, x_lb=None, x_ub=None):
