@@ -88,4 +88,47 @@ MMPC_TRIG_FN void sincos_fast(trig_cptr K, double x, double* s, double* c) {
     *c = ((q + 1) & 2) ? -b : b;
 }
 
+// W arguments at once: sincos_fast's operations in its order, each applied to the W elements in turn, so that W
+// independent chains alternate in the instruction stream (a dependent FP64 FMA waits 11 cycles, an independent one
+// issues after 4).  Element e gets the values sincos_fast(K, x[e], ..) gives, bit for bit.
+template <int W>
+MMPC_TRIG_FN void sincos_fast_w(trig_cptr K, const double* x, double* s, double* c) {
+#if !defined(__HIPCC__) && !defined(MMPC_TRIG_DEVICE_PATH_ON_HOST)
+    for (int e = 0; e < W; ++e) sincos_fast(K, x[e], s + e, c + e);   // (libm beyond the domain, per element)
+#else
+#define MMPC_W for (int e = 0; e < W; ++e)
+    double n[W], r[W], z[W], ps[W], pc[W], sr[W], cr[W];
+    MMPC_W n[e] = rint(x[e] * K[0]);
+    MMPC_W r[e] = fma(-n[e], K[1], x[e]);
+    MMPC_W r[e] = fma(-n[e], K[2], r[e]);
+    MMPC_W r[e] = fma(-n[e], K[3], r[e]);
+    MMPC_W r[e] = fabs(x[e]) <= 1647099.3291652855 ? r[e] : __builtin_nan("");
+    MMPC_W z[e] = r[e] * r[e];
+    // the two polynomials of an element are independent as well: their steps alternate too
+    MMPC_W ps[e] = fma(z[e], K[9], K[8]);
+    MMPC_W pc[e] = fma(z[e], K[15], K[14]);
+    MMPC_W ps[e] = fma(z[e], ps[e], K[7]);
+    MMPC_W pc[e] = fma(z[e], pc[e], K[13]);
+    MMPC_W ps[e] = fma(z[e], ps[e], K[6]);
+    MMPC_W pc[e] = fma(z[e], pc[e], K[12]);
+    MMPC_W ps[e] = fma(z[e], ps[e], K[5]);
+    MMPC_W pc[e] = fma(z[e], pc[e], K[11]);
+    MMPC_W sr[e] = fma(z[e] * r[e], fma(z[e], ps[e], K[4]), r[e]);
+    MMPC_W pc[e] = z[e] * fma(z[e], pc[e], K[10]);
+    MMPC_W {
+        const double hz = 0.5 * z[e];
+        const double w = 1.0 - hz;
+        cr[e] = w + (((1.0 - w) - hz) + z[e] * pc[e]);
+    }
+    MMPC_W {
+        const int q = (int)fma(-4.0, floor(0.25 * n[e]), n[e]);
+        const bool odd = (q & 1) != 0;
+        const double a = odd ? cr[e] : sr[e], b = odd ? sr[e] : cr[e];
+        s[e] = (q & 2) ? -a : a;
+        c[e] = ((q + 1) & 2) ? -b : b;
+    }
+#undef MMPC_W
+#endif
+}
+
 }  // namespace mmpc

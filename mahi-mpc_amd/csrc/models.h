@@ -22,7 +22,10 @@ struct TwoLinkArm {
     static constexpr int NX = 4;
     static constexpr int NU = 2;
     static constexpr int NQ = 2;  // second-order: x = [q; qd], xdot = [qd; acc(x, u)]
-    MMPC_HD static void eval(const double* x, const double* u, double* xd) { TwoLinkFast::eval(x, u, xd); }
+    // eval, eval_acc_jac and eval_hess also take dpack<W> values (two_link_fast.h): W points with their chains in turn
+    static constexpr bool kWideEval = true;
+    template <class T>
+    MMPC_HD static void eval(const T* x, const T* u, T* xd) { TwoLinkFast::eval(x, u, xd); }
     MMPC_HD static void eval_jac(const double* x, const double* u, double* xd, double* fx, double* fu) {
         double Fq[4], Fqd[4], Fu[4];
         TwoLinkFast::eval_acc_jac(x, u, xd + 2, Fq, Fqd, Fu);
@@ -42,14 +45,15 @@ struct TwoLinkArm {
         }
     }
     // acceleration and its partials d acc/dq [NQ*NQ], d acc/dqd [NQ*NQ], d acc/du [NQ*NU] (row-major)
-    MMPC_HD static void eval_acc_jac(const double* x, const double* u, double* acc, double* Fq, double* Fqd,
-                                     double* Fu) {
+    template <class T>
+    MMPC_HD static void eval_acc_jac(const T* x, const T* u, T* acc, T* Fq, T* Fqd, T* Fu) {
         TwoLinkFast::eval_acc_jac(x, u, acc, Fq, Fqd, Fu);
     }
     // W = sum_s lam[s] d^2 acc_s / d(x, u)^2 (6 x 6 row-major): the dynamics part of the Lagrangian Hessian
     // (CasADi nlp_hess_l, ModelGenerator.cpp:238)
     static constexpr bool kHasHess = true;
-    MMPC_HD static void eval_hess(const double* x, const double* u, const double* lam, double* W) {
+    template <class T>
+    MMPC_HD static void eval_hess(const T* x, const T* u, const T* lam, T* W) {
         TwoLinkFast::eval_hess(x, u, lam, W);
     }
     // acc is affine in the torques (acc = M(q)^-1 (T - ...)), so the u-u block of every W is exactly zero
@@ -63,6 +67,15 @@ struct HasHess {
 };
 template <class M>
 struct HasHess<M, std::enable_if_t<M::kHasHess>> {
+    static constexpr bool value = true;
+};
+// Model functions that take W points at once (dpack<W> values, two_link_fast.h): the 16-lane kernel's paired stages
+template <class M, class = void>
+struct HasWideEval {
+    static constexpr bool value = false;
+};
+template <class M>
+struct HasWideEval<M, std::enable_if_t<M::kWideEval>> {
     static constexpr bool value = true;
 };
 // Dynamics affine in u (d^2 acc / du^2 == 0): the exact-Hessian sweep skips the u-u block of W_k, which is zero

@@ -270,6 +270,59 @@ __device__ __forceinline__ void group_model(bool lin, const double* lFq, const d
     }
 }
 
+// The model at the W stages of a pair (PAIR, sqp_group_kernel): x, u, xd and the blocks per stage [e].  W = 1 is
+// group_model itself, with its run-time `lin` (LM < 0).  W > 1 takes `lin` as the constant LM, hoisted out of the stage
+// loop by the caller (as a branch inside the body it would split the pair's block and keep the chains apart): LM = 0
+// evaluates the model once on dpack<W> values, so the W chains alternate operation by operation (two_link_fast.h);
+// LM = 1 is the linear-mode branch of group_model per stage.  Stage e gets group_model's values bit for bit.
+template <class Model, int W, int LM, bool JAC, int SQ, int FD, int FU>
+__device__ __forceinline__ void group_model_w(bool lin, const double* lFq, const double* lFqd, const double* lFu,
+                                              const double* lxd, const double* lxs, const double* lus,
+                                              const double (*x)[Model::NX], const double (*u)[Model::NU],
+                                              double (*xd)[Model::NX], double (*Fq)[SQ], double (*Fqd)[FD],
+                                              double (*Fu)[FU]) {
+    constexpr int NX = Model::NX, NQ = Model::NQ, NU = Model::NU, NA = NX - NQ;
+    if constexpr (W == 1 || LM != 0) {
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+            group_model<Model>(W == 1 ? lin : true, lFq, lFqd, lFu, lxd, lxs, lus, x[e], u[e], xd[e], JAC ? Fq[e] : nullptr,
+                               JAC ? Fqd[e] : nullptr, JAC ? Fu[e] : nullptr, JAC);
+    } else {
+        using T = dpack<W>;
+        T xw[NX], uw[NU], xdw[NX];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xw[i].v[e] = x[e][i];
+#pragma unroll
+            for (int i = 0; i < NU; ++i) uw[i].v[e] = u[e][i];
+        }
+        if constexpr (JAC) {
+            T fq[SQ], fqd[FD], fu[FU];
+            Model::eval_acc_jac(xw, uw, xdw + NQ, fq, fqd, fu);
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) xd[e][i] = x[e][NQ + i];
+#pragma unroll
+                for (int i = 0; i < NA; ++i) xd[e][NQ + i] = xdw[NQ + i].v[e];
+#pragma unroll
+                for (int i = 0; i < NA * NQ; ++i) Fq[e][i] = fq[i].v[e];
+#pragma unroll
+                for (int i = 0; i < FD; ++i) Fqd[e][i] = fqd[i].v[e];
+#pragma unroll
+                for (int i = 0; i < FU; ++i) Fu[e][i] = fu[i].v[e];
+            }
+        } else {
+            Model::eval(xw, uw, xdw);
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+#pragma unroll
+                for (int i = 0; i < NX; ++i) xd[e][i] = xdw[i].v[e];
+        }
+    }
+}
+
 // XB: state bounds (oracle solve_one_ip), the primal-dual interior-point variant for state AND control bounds;
 // BOUNDED: control bounds only (projected GN-SQP).  At most one of them.
 // EXACT: exact Hessian of the Lagrangian (mmpc_opts.hessian; oracle ORACLE_HESS_EXACT) -- solves of models with
@@ -379,6 +432,11 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     [[maybe_unused]] double* const sVr = sCu + N * NY;   // [N][VR]
     const double* const trg = p.traj + ii * (int64_t)N * NX;
 
+    // two stages per lane in the stage-parallel phases (at FUSE_FWD, below)
+    constexpr bool PAIR = HasWideEval<Model>::value && !BOUNDED && !XB;
+    constexpr int WD = PAIR ? 2 : 1;
+    // width of phase A, of the fused trial and of the W pass (1 takes one of them back to its one-stage loop)
+    constexpr int WA = WD, WJ = WD, WW = WD;
     const double* w = p.weights + ii * p.w_stride;
     double Q[NX], R[NU], Rm[NU], up[NU];
 #pragma unroll
@@ -391,6 +449,47 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     }
     double lbv[NU], ubv[NU];
     load_bounds<NU, BOUNDED, IB>(p, inst, lbv, ubv);
+    // PAIR: the prologue in one round trip.  Every global load of the lane is issued here, behind the weights and u_prev
+    // and before anything waits for one of them: x_0, and for the lane's first pair of stages (gl and gl + G: the whole
+    // horizon up to N = 2 G - 1) the targets and, unless the start is zero, V.  The LDS stores and the per-lane
+    // constants derived from the weights follow.  The uniform init_zero test is taken once, around the loads; a stage
+    // index past the horizon is clamped (k to the lane's first stage, the u / target row of k = N to N - 1), so the
+    // loads need no lane test and a repeated store writes the value already there.
+    [[maybe_unused]] double px0[NX], pxv[WD][NX], puv[WD][NU], prv[WD][NX];
+    // (a lane past the end of a short horizon, gl > N, loads stage N's values and stores nothing)
+    [[maybe_unused]] auto pro_k = [&](int k0, int e) { return k0 + e * G <= N ? k0 + e * G : (k0 <= N ? k0 : N); };
+    [[maybe_unused]] auto pro_load = [&](int k0, double (*xv)[NX], double (*uv)[NU], double (*rv)[NX]) {
+        const double* Vin = p.V + ii * (int64_t)NV;
+#pragma unroll
+        for (int e = 0; e < WD; ++e) {
+            const int k = pro_k(k0, e), ku = k < N ? k : N - 1;
+#pragma unroll
+            for (int r = 0; r < NX; ++r) rv[e][r] = trg[ku * NX + r];
+        }
+        if (p.init_zero) {
+#pragma unroll
+            for (int e = 0; e < WD; ++e) {
+#pragma unroll
+                for (int r = 0; r < NX; ++r) xv[e][r] = 0.0;
+#pragma unroll
+                for (int c = 0; c < NU; ++c) uv[e][c] = 0.0;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < WD; ++e) {
+                const int k = pro_k(k0, e), ku = k < N ? k : N - 1;
+#pragma unroll
+                for (int r = 0; r < NX; ++r) xv[e][r] = Vin[k * ND + r];
+#pragma unroll
+                for (int c = 0; c < NU; ++c) uv[e][c] = Vin[ku * ND + NX + c];
+            }
+        }
+    };
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int r = 0; r < NX; ++r) px0[r] = p.x0[ii * NX + r];
+        pro_load(gl, pxv, puv, prv);
+    }
     // ---- lane-distributed Riccati (DIST): lane r of the group owns row r of the augmented value function
     //      P~ (NS x NS) and of every per-row quantity; small per-stage quantities are computed redundantly on
     //      all lanes; rows are exchanged with row_bcast.  Control bounds (BOUNDED) run the same
@@ -497,7 +596,24 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         for (int i = gl; i < KC; i += G) sKc[i] = (i == NX - 1) ? h : 0.0;
     }
     // ---- load: V (reference layout) -> LDS, x_0 pinned (ModelControl.cpp:144-145) ----
-    {
+    if constexpr (PAIR) {
+        // the first pair's values are in flight since the top (pro_load); a horizon of more than two rounds loads its
+        // further pairs here, one round trip each
+        const bool hold = p.init_hold != 0;
+        for (int k0 = gl; k0 <= N; k0 += WD * G) {
+            if (k0 != gl) pro_load(k0, pxv, puv, prv);
+#pragma unroll
+            for (int e = 0; e < WD; ++e) {
+                const int k = pro_k(k0, e), ku = k < N ? k : N - 1;
+#pragma unroll
+                for (int r = 0; r < NX; ++r) sX[k * NX + r] = (k == 0 || hold) ? px0[r] : pxv[e][r];
+#pragma unroll
+                for (int c = 0; c < NU; ++c) sU[ku * NU + c] = puv[e][c];
+#pragma unroll
+                for (int r = 0; r < NX; ++r) sR[ku * NX + r] = prv[e][r];
+            }
+        }
+    } else {
         const double* Vin = p.V + ii * (int64_t)NV;
         for (int k = gl; k <= N; k += G) {
 #pragma unroll
@@ -580,6 +696,22 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // fma(alpha, dy, y) (ip_update), so the fused evaluation is again phase A's; the barrier terms (ip_terms) of phase
     // A still run every iteration, after the dual update.
     constexpr bool FUSE_FWD = true;
+    // PAIR: the stage-parallel phases take TWO stages per lane in one straight-line body, k and k + G (the unbounded
+    // solves of a model whose functions take dpack values, HasWideEval: the 2-link arm, cfg#2).  A lane's stage
+    // evaluation is one dependent FP64 chain (two range reductions, four Horner polynomials, a division, the quotient
+    // rule) that issues every ~8 cycles where the wave could issue every 4; the second stage is an independent chain
+    // in the same block, interleaved in the source (group_model_w).  A lane without a second stage (k + G >= N) repeats
+    // its own stage k: it stores the same values to the same addresses, the max and non-finite accumulators are
+    // idempotent, and the sums (J, |c|_1, dJ) keep their value after the first stage by one select each.  Per stage
+    // every operation keeps its operands and order, and every per-lane sum its order (k, then k + G).  For N > 2 G the
+    // loops run over pairs of rounds.  WD = 1 (every other kernel) is the one-stage loop as it was.  (PAIR and WD are
+    // defined at the prologue, which takes the pairs too.)
+    // the stage loops' body with `lin` hoisted (PAIR) or as group_model's run-time argument (LM = -1)
+    auto with_lin = [&](auto wd_c, auto&& body) {
+        if constexpr (decltype(wd_c)::value == 1) body(std::integral_constant<int, -1>{});
+        else if (p.is_linear != 0) body(std::integral_constant<int, 1>{});
+        else body(std::integral_constant<int, 0>{});
+    };
     bool fwd_ready = false;
     double J0n = 0.0, c1n = 0.0, cmaxn = 0.0;
     int nfn = 0;
@@ -596,38 +728,64 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             c1 = 0.0;
             cmax = 0.0;
             nonfinite = 0;
-            for (int k = gl; k < N; k += G) {
-                double x[NX], u[NU], xd[NX], Fq[SQ], Fqd[FD], Fu[FU];
+            with_lin(std::integral_constant<int, WA>{}, [&](auto lm_c) {
+                constexpr int LM = decltype(lm_c)::value;
+                for (int k0 = gl; k0 < N; k0 += WA * G) {
+                    int kk[WA];
+                    double x[WA][NX], u[WA][NU], xd[WA][NX], Fq[WA][SQ], Fqd[WA][FD], Fu[WA][FU];
 #pragma unroll
-                for (int r = 0; r < NX; ++r) x[r] = sX[k * NX + r];
+                    for (int e = 0; e < WA; ++e) {
+                        kk[e] = (e == 0 || k0 + e * G < N) ? k0 + e * G : k0;
 #pragma unroll
-                for (int c = 0; c < NU; ++c) u[c] = sU[k * NU + c];
-                group_model<Model>(lin, lFq, lFqd, lFu, lxd, lxs, up, x, u, xd, Fq, Fqd, Fu, true);
+                        for (int r = 0; r < NX; ++r) x[e][r] = sX[kk[e] * NX + r];
 #pragma unroll
-                for (int i = 0; i < FQ; ++i) sFq[k * FQ + i] = h * Fq[i];
+                        for (int c = 0; c < NU; ++c) u[e][c] = sU[kk[e] * NU + c];
+                    }
+                    group_model_w<Model, WA, LM, true, SQ, FD, FU>(lin, lFq, lFqd, lFu, lxd, lxs, up, x, u, xd, Fq, Fqd, Fu);
+                    double cd[WA][NX], er[WA][NX];
 #pragma unroll
-                for (int i = 0; i < FD; ++i) sFqd[k * FD + i] = h * Fqd[i];
+                    for (int e = 0; e < WA; ++e) {
+                        const int k = kk[e];
 #pragma unroll
-                for (int i = 0; i < FU; ++i) sFu[k * FU + i] = h * Fu[i];
+                        for (int i = 0; i < FQ; ++i) sFq[k * FQ + i] = h * Fq[e][i];
 #pragma unroll
-                for (int r = 0; r < NX; ++r) {
-                    const double F = fma(h, xd[r], x[r]);
-                    sF[k * NX + r] = F;
-                    const double c = F - sX[(k + 1) * NX + r];
-                    sC[k * NX + r] = c;
-                    cmax = fmax(cmax, fabs(c));
-                    c1 += fabs(c);
-                    nonfinite |= !isfinite(c);
-                    const double e = F - tr[k * NX + r];
-                    J0 = fma(e * Q[r], e, J0);
+                        for (int i = 0; i < FD; ++i) sFqd[k * FD + i] = h * Fqd[e][i];
+#pragma unroll
+                        for (int i = 0; i < FU; ++i) sFu[k * FU + i] = h * Fu[e][i];
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) {
+                            const double F = fma(h, xd[e][r], x[e][r]);
+                            sF[k * NX + r] = F;
+                            cd[e][r] = F - sX[(k + 1) * NX + r];
+                            sC[k * NX + r] = cd[e][r];
+                            er[e][r] = F - tr[k * NX + r];
+                        }
+                    }
+                    // the sums in stage order; a repeated stage leaves them as they were
+#pragma unroll
+                    for (int e = 0; e < WA; ++e) {
+                        const int k = kk[e];
+                        double Js = J0, cs = c1;
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) {
+                            const double c = cd[e][r];
+                            cmax = fmax(cmax, fabs(c));
+                            cs += fabs(c);
+                            nonfinite |= !isfinite(c);
+                            Js = fma(er[e][r] * Q[r], er[e][r], Js);
+                        }
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) {
+                            const double um = (k == 0) ? up[c] : sU[(k - 1) * NU + c];
+                            const double dif = u[e][c] - um;
+                            Js = fma(dif * R[c], dif, fma(u[e][c] * Rm[c], u[e][c], Js));
+                        }
+                        const bool on = e == 0 || k0 + e * G < N;
+                        J0 = on ? Js : J0;
+                        c1 = on ? cs : c1;
+                    }
                 }
-#pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    const double um = (k == 0) ? up[c] : sU[(k - 1) * NU + c];
-                    const double dif = u[c] - um;
-                    J0 = fma(dif * R[c], dif, fma(u[c] * Rm[c], u[c], J0));
-                }
-            }
+            });
         }
         double lsum = 0.0, cmpl0 = 0.0, cmplmu = 0.0;  // interior point: sum log s, max |s z|, max |s z - mu|
         if constexpr (XB) {
@@ -1876,46 +2034,84 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             // only overwrite the lam operands of stages k' >= k.  The stages are therefore taken in rounds of 16 from the
             // last round down, for every N: the stages above a round are done, and within a round every lane's lam loads
             // precede every lane's stores in program order (one wave; LDS serves its accesses in order).
-            auto w_stage = [&](int k) {
-                double x[NX], u[NU], la[NA], W[KZ * KZ];
+            // PAIR: a lane takes the stages k0 + gl and k0 + G + gl of two rounds together (kk[0], kk[1]; the first again when
+            // the second is past the horizon), from the last pair of rounds down.  The argument holds for the pair as for
+            // the round: the pairs of rounds above are done; inside the pair every lane's lam loads of BOTH stages precede
+            // every lane's stores in program order, and the stores reach only lam operands of stages >= the pair's lowest,
+            // all of them loaded or done.  A repeated stage stores its record twice, with the same values.
+            auto w_stages = [&](const int (&kk)[WW]) {
+                double x[WW][NX], u[WW][NU], la[WW][NA], W[WW][KZ * KZ];
 #pragma unroll
-                for (int r2 = 0; r2 < NX; ++r2) x[r2] = sX[k * NX + r2];
+                for (int e = 0; e < WW; ++e) {
+                    const int k = kk[e];
 #pragma unroll
-                for (int c = 0; c < NU; ++c) u[c] = sU[k * NU + c];
+                    for (int r2 = 0; r2 < NX; ++r2) x[e][r2] = sX[k * NX + r2];
 #pragma unroll
-                for (int s2 = 0; s2 < NA; ++s2) la[s2] = h * sD[(k + 1) * NX + NQ + s2];
+                    for (int c = 0; c < NU; ++c) u[e][c] = sU[k * NU + c];
+#pragma unroll
+                    for (int s2 = 0; s2 < NA; ++s2) la[e][s2] = h * sD[(k + 1) * NX + NQ + s2];
+                }
                 if constexpr (WLDS) __builtin_amdgcn_wave_barrier();   // (compiler: no store of this round above a load)
-                Model::eval_hess(x, u, la, W);
-                if constexpr (WLDS) {
-                    static_assert(!WLDS || PK >= NX, "write order of the W pass");
+                if constexpr (WW == 1) {
+                    Model::eval_hess(x[0], u[0], la[0], W[0]);
+                } else {   // the WW evaluations with their chains in turn (two_link_fast.h)
+                    using T = dpack<WW>;
+                    T xw[NX], uw[NU], lw[NA], Ww[KZ * KZ];
 #pragma unroll
-                    for (int r2 = 0; r2 < NX; ++r2)
+                    for (int e = 0; e < WW; ++e) {
 #pragma unroll
-                        for (int j = r2; j < KZ; ++j)
-                            if (WPack<Model>::idx(r2, j) >= 0) sW[k * PK + WPack<Model>::idx(r2, j)] = W[r2 * KZ + j];
-                } else {
-                    double* const dst = wH + k * HW;
+                        for (int i = 0; i < NX; ++i) xw[i].v[e] = x[e][i];
 #pragma unroll
-                    for (int r2 = 0; r2 < NX; ++r2)
+                        for (int i = 0; i < NU; ++i) uw[i].v[e] = u[e][i];
 #pragma unroll
-                        for (int j = 0; j < KZ; ++j)
-                            if (!w_struct_zero<Model>(r2, j) || !w_zeros_stored) dst[r2 * KZ + j] = W[r2 * KZ + j];
-                    if constexpr (!CAFF) {
+                        for (int i = 0; i < NA; ++i) lw[i].v[e] = la[e][i];
+                    }
+                    Model::eval_hess(xw, uw, lw, Ww);
 #pragma unroll
-                        for (int a = 0; a < NU; ++a)
+                    for (int e = 0; e < WW; ++e)
 #pragma unroll
-                            for (int b = 0; b < NU; ++b) dst[NX * KZ + a * NU + b] = W[(NX + a) * KZ + NX + b];
+                        for (int i = 0; i < KZ * KZ; ++i) W[e][i] = Ww[i].v[e];
+                }
+#pragma unroll
+                for (int e = 0; e < WW; ++e) {
+                    const int k = kk[e];
+                    if constexpr (WLDS) {
+                        static_assert(!WLDS || PK >= NX, "write order of the W pass");
+#pragma unroll
+                        for (int r2 = 0; r2 < NX; ++r2)
+#pragma unroll
+                            for (int j = r2; j < KZ; ++j)
+                                if (WPack<Model>::idx(r2, j) >= 0) sW[k * PK + WPack<Model>::idx(r2, j)] = W[e][r2 * KZ + j];
+                    } else {
+                        double* const dst = wH + k * HW;
+#pragma unroll
+                        for (int r2 = 0; r2 < NX; ++r2)
+#pragma unroll
+                            for (int j = 0; j < KZ; ++j)
+                                if (!w_struct_zero<Model>(r2, j) || !w_zeros_stored) dst[r2 * KZ + j] = W[e][r2 * KZ + j];
+                        if constexpr (!CAFF) {
+#pragma unroll
+                            for (int a = 0; a < NU; ++a)
+#pragma unroll
+                                for (int b = 0; b < NU; ++b) dst[NX * KZ + a * NU + b] = W[e][(NX + a) * KZ + NX + b];
+                        }
                     }
                 }
             };
+            auto w_pair = [&](int k0) {   // the lane's stages of the WW rounds from k0 (= its stage of the first)
+                int kk[WW];
+#pragma unroll
+                for (int e = 0; e < WW; ++e) kk[e] = (e == 0 || k0 + e * G < N) ? k0 + e * G : k0;
+                w_stages(kk);
+            };
             if constexpr (WLDS) {
-                for (int k0 = ((N - 1) / G) * G; k0 >= 0; k0 -= G)
-                    if (k0 + gl < N) w_stage(k0 + gl);
+                for (int k0 = ((N - 1) / (WW * G)) * (WW * G); k0 >= 0; k0 -= WW * G)
+                    if (k0 + gl < N) w_pair(k0 + gl);
                 MMPC_PHASE(9);   // (timing build: "check" = the stop test and this W pass)
                 // the records of the other lanes of this wave are in LDS before the sweep's loads: program order
                 __builtin_amdgcn_wave_barrier();
             } else {
-                for (int k = gl; k < N; k += G) w_stage(k);
+                for (int k = gl; k < N; k += WW * G) w_pair(k);
                 w_zeros_stored = true;
                 MMPC_PHASE(9);   // (timing build: "check" = the stop test and this W pass up to its fence)
                 // the stores of the other lanes of this wave must be visible to the sweep's loads
@@ -2245,15 +2441,33 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             // directional derivative of J along (dx, du), stage-parallel:
             // sum_k 2Q(F_k - r_k).(A dx_k + B du_k) + 2R(u_k - u_{k-1})(du_k - du_{k-1}) + 2Rm u_k du_k
             double dj = 0.0;
-            for (int k = gl; k < N; k += G) {
+            for (int k0 = gl; k0 < N; k0 += WD * G) {   // (PAIR: the loads of two stages in flight together)
+                double ef[WD][NX], ad[WD][NX], uk[WD][NU], duk[WD][NU], um[WD][NU], dum[WD][NU];
 #pragma unroll
-                for (int q = 0; q < NX; ++q) dj = fma(2.0 * Q[q] * (sF[k * NX + q] - tr[k * NX + q]), sD[(k + 1) * NX + q], dj);
+                for (int e = 0; e < WD; ++e) {
+                    const int k = (e == 0 || k0 + e * G < N) ? k0 + e * G : k0;
 #pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    const double uk = sU[k * NU + c], duk = sDU[k * NU + c];
-                    const double um = (k == 0) ? up[c] : sU[(k - 1) * NU + c];
-                    const double dum = (k == 0) ? 0.0 : sDU[(k - 1) * NU + c];
-                    dj = fma(2.0 * R[c] * (uk - um), duk - dum, fma(2.0 * Rm[c] * uk, duk, dj));
+                    for (int q = 0; q < NX; ++q) {
+                        ef[e][q] = sF[k * NX + q] - tr[k * NX + q];
+                        ad[e][q] = sD[(k + 1) * NX + q];
+                    }
+#pragma unroll
+                    for (int c = 0; c < NU; ++c) {
+                        uk[e][c] = sU[k * NU + c];
+                        duk[e][c] = sDU[k * NU + c];
+                        um[e][c] = (k == 0) ? up[c] : sU[(k - 1) * NU + c];
+                        dum[e][c] = (k == 0) ? 0.0 : sDU[(k - 1) * NU + c];
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < WD; ++e) {
+                    double ds = dj;
+#pragma unroll
+                    for (int q = 0; q < NX; ++q) ds = fma(2.0 * Q[q] * ef[e][q], ad[e][q], ds);
+#pragma unroll
+                    for (int c = 0; c < NU; ++c)
+                        ds = fma(2.0 * R[c] * (uk[e][c] - um[e][c]), duk[e][c] - dum[e][c], fma(2.0 * Rm[c] * uk[e][c], duk[e][c], ds));
+                    dj = (e == 0 || k0 + e * G < N) ? ds : dj;
                 }
             }
             dJ = group_sum(dj);
@@ -2309,61 +2523,92 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
         int nft = 0;
         auto trial = [&](auto jac_c, double& Jt, double& ct, double& lt) {
             constexpr bool JAC = decltype(jac_c)::value;
-            for (int k = gl; k < N; k += G) {
-                double x[NX], u[NU], xd[NX];
+            // two stages per lane in the fused trial; the trials after a rejected full step keep the one-stage loop (no
+            // cfg#2 iteration runs them, and with nothing to store the compiler puts a pair's second evaluation behind a
+            // branch on "the lane has a second stage" anyway)
+            constexpr int WT = JAC ? WJ : 1;
+            with_lin(std::integral_constant<int, WT>{}, [&](auto lm_c) {
+                constexpr int LM = decltype(lm_c)::value;
+                for (int k0 = gl; k0 < N; k0 += WT * G) {
+                    int kk[WT];
+                    double x[WT][NX], u[WT][NU], xd[WT][NX];
+                    [[maybe_unused]] double Fq[WT][SQ], Fqd[WT][FD], Fu[WT][FU];
 #pragma unroll
-                for (int r = 0; r < NX; ++r) x[r] = fma(alpha, sDX[k * NX + r], sX[k * NX + r]);
+                    for (int e = 0; e < WT; ++e) {
+                        const int k = kk[e] = (e == 0 || k0 + e * G < N) ? k0 + e * G : k0;
 #pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    u[c] = fma(alpha, sDU[k * NU + c], sU[k * NU + c]);
-                    if (BOUNDED) u[c] = proj(u[c], lbv[c], ubv[c]);  // projected trial point
-                }
-                if constexpr (JAC) {   // = phase A at the trial point (stored for the next iteration)
-                    double Fq[SQ], Fqd[FD], Fu[FU];
-                    group_model<Model>(lin, lFq, lFqd, lFu, lxd, lxs, up, x, u, xd, Fq, Fqd, Fu, true);
+                        for (int r = 0; r < NX; ++r) x[e][r] = fma(alpha, sDX[k * NX + r], sX[k * NX + r]);
 #pragma unroll
-                    for (int i = 0; i < FQ; ++i) sFq[k * FQ + i] = h * Fq[i];
-#pragma unroll
-                    for (int i = 0; i < FD; ++i) sFqd[k * FD + i] = h * Fqd[i];
-#pragma unroll
-                    for (int i = 0; i < FU; ++i) sFu[k * FU + i] = h * Fu[i];
-#pragma unroll
-                    for (int r = 0; r < NX; ++r) {
-                        const double F = fma(h, xd[r], x[r]);
-                        sF[k * NX + r] = F;
-                        const double c = F - fma(alpha, sDX[(k + 1) * NX + r], sX[(k + 1) * NX + r]);
-                        sC[k * NX + r] = c;
-                        ctm = fmax(ctm, fabs(c));
-                        ct += fabs(c);
-                        nft |= !isfinite(c);
-                        const double er = F - tr[k * NX + r];
-                        Jt = fma(er * Q[r], er, Jt);
+                        for (int c = 0; c < NU; ++c) {
+                            u[e][c] = fma(alpha, sDU[k * NU + c], sU[k * NU + c]);
+                            if (BOUNDED) u[e][c] = proj(u[e][c], lbv[c], ubv[c]);  // projected trial point
+                        }
                     }
-                } else {
-                    group_model<Model>(lin, lFq, lFqd, lFu, lxd, lxs, up, x, u, xd, nullptr, nullptr, nullptr, false);
+                    group_model_w<Model, WT, LM, JAC, SQ, FD, FU>(lin, lFq, lFqd, lFu, lxd, lxs, up, x, u, xd, Fq, Fqd, Fu);
+                    double cd[WT][NX], er[WT][NX];
 #pragma unroll
-                    for (int r = 0; r < NX; ++r) {
-                        const double F = fma(h, xd[r], x[r]);
-                        const double er = F - tr[k * NX + r];
-                        Jt = fma(er * Q[r], er, Jt);
-                        ct += fabs(F - fma(alpha, sDX[(k + 1) * NX + r], sX[(k + 1) * NX + r]));
+                    for (int e = 0; e < WT; ++e) {
+                        const int k = kk[e];
+                        if constexpr (JAC) {   // = phase A at the trial point (stored for the next iteration)
+#pragma unroll
+                            for (int i = 0; i < FQ; ++i) sFq[k * FQ + i] = h * Fq[e][i];
+#pragma unroll
+                            for (int i = 0; i < FD; ++i) sFqd[k * FD + i] = h * Fqd[e][i];
+#pragma unroll
+                            for (int i = 0; i < FU; ++i) sFu[k * FU + i] = h * Fu[e][i];
+                        }
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) {
+                            const double F = fma(h, xd[e][r], x[e][r]);
+                            if constexpr (JAC) sF[k * NX + r] = F;
+                            if constexpr (JAC) {
+                                cd[e][r] = F - fma(alpha, sDX[(k + 1) * NX + r], sX[(k + 1) * NX + r]);
+                                sC[k * NX + r] = cd[e][r];
+                                er[e][r] = F - tr[k * NX + r];
+                            } else {
+                                er[e][r] = F - tr[k * NX + r];
+                                cd[e][r] = F - fma(alpha, sDX[(k + 1) * NX + r], sX[(k + 1) * NX + r]);
+                            }
+                        }
+                    }
+                    // the sums in stage order; a repeated stage leaves them as they were
+#pragma unroll
+                    for (int e = 0; e < WT; ++e) {
+                        const int k = kk[e];
+                        double Js = Jt, cs = ct, ls = lt;
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) {
+                            if constexpr (JAC) {
+                                ctm = fmax(ctm, fabs(cd[e][r]));
+                                cs += fabs(cd[e][r]);
+                                nft |= !isfinite(cd[e][r]);
+                                Js = fma(er[e][r] * Q[r], er[e][r], Js);
+                            } else {
+                                Js = fma(er[e][r] * Q[r], er[e][r], Js);
+                                cs += fabs(cd[e][r]);
+                            }
+                        }
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) {
+                            double um = (k == 0) ? up[c] : fma(alpha, sDU[(k - 1) * NU + c], sU[(k - 1) * NU + c]);
+                            if (BOUNDED && k > 0) um = proj(um, lbv[c], ubv[c]);
+                            const double dif = u[e][c] - um;
+                            Js = fma(dif * R[c], dif, fma(u[e][c] * Rm[c], u[e][c], Js));
+                        }
+                        if constexpr (XB) {
+#pragma unroll
+                            for (int j = 0; j < NY; ++j) {
+                                const double y = j < NX ? fma(alpha, sDX[(k + 1) * NX + j], sX[(k + 1) * NX + j]) : u[e][j - NX];
+                                ls += ip_log_slacks(y, yl[j], yu[j]);
+                            }
+                        }
+                        const bool on = e == 0 || k0 + e * G < N;
+                        Jt = on ? Js : Jt;
+                        ct = on ? cs : ct;
+                        lt = on ? ls : lt;
                     }
                 }
-#pragma unroll
-                for (int c = 0; c < NU; ++c) {
-                    double um = (k == 0) ? up[c] : fma(alpha, sDU[(k - 1) * NU + c], sU[(k - 1) * NU + c]);
-                    if (BOUNDED && k > 0) um = proj(um, lbv[c], ubv[c]);
-                    const double dif = u[c] - um;
-                    Jt = fma(dif * R[c], dif, fma(u[c] * Rm[c], u[c], Jt));
-                }
-                if constexpr (XB) {
-#pragma unroll
-                    for (int j = 0; j < NY; ++j) {
-                        const double y = j < NX ? fma(alpha, sDX[(k + 1) * NX + j], sX[(k + 1) * NX + j]) : u[j - NX];
-                        lt += ip_log_slacks(y, yl[j], yu[j]);
-                    }
-                }
-            }
+            });
         };
         bool jac_trial = false;
         for (int ls = 0; ls < 30; ++ls) {
@@ -2420,16 +2665,46 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             }
             if constexpr (!MEHR) mub = mub_next;   // MEHR: no lagged update, mu_t is set in every iteration
         } else {
-            for (int k = gl; k <= N; k += G) {
-                if (k > 0) {
+            // (PAIR: all loads of the two stages before their stores -- a repeated stage forms its new value from the old
+            // one both times and stores it twice)
+            for (int k0 = gl; k0 <= N; k0 += WD * G) {
+                int kk[WD], ku[WD];
+                double xn[WD][NX], un[WD][NU];
 #pragma unroll
-                    for (int r = 0; r < NX; ++r) sX[k * NX + r] = fma(alpha, sDX[k * NX + r], sX[k * NX + r]);
+                for (int e = 0; e < WD; ++e) {
+                    const int k = kk[e] = (e == 0 || k0 + e * G <= N) ? k0 + e * G : k0;
+                    if constexpr (WD == 1) {
+                        ku[e] = k;
+                        if (k > 0) {
+#pragma unroll
+                            for (int r = 0; r < NX; ++r) xn[e][r] = fma(alpha, sDX[k * NX + r], sX[k * NX + r]);
+                        }
+                        if (k < N) {
+#pragma unroll
+                            for (int c = 0; c < NU; ++c) un[e][c] = fma(alpha, sDU[k * NU + c], sU[k * NU + c]);
+                        }
+                    } else {   // loads without lane tests: x_0 keeps its bytes by a select, k = N reads the u row of N - 1
+                        ku[e] = k < N ? k : N - 1;
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) {
+                            const double xo = sX[k * NX + r];
+                            xn[e][r] = k > 0 ? fma(alpha, sDX[k * NX + r], xo) : xo;
+                        }
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) un[e][c] = fma(alpha, sDU[ku[e] * NU + c], sU[ku[e] * NU + c]);
+                    }
                 }
-                if (k < N) {
+                if constexpr (WD > 1) __builtin_amdgcn_wave_barrier();   // (compiler: no store of the pair above a load)
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) {
-                        const double un = fma(alpha, sDU[k * NU + c], sU[k * NU + c]);
-                        sU[k * NU + c] = BOUNDED ? proj(un, lbv[c], ubv[c]) : un;
+                for (int e = 0; e < WD; ++e) {
+                    const int k = kk[e];
+                    if (WD > 1 || k > 0) {
+#pragma unroll
+                        for (int r = 0; r < NX; ++r) sX[k * NX + r] = xn[e][r];
+                    }
+                    if (k < N) {   // (never the u row of another lane's stage: that lane updates it itself)
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) sU[ku[e] * NU + c] = BOUNDED ? proj(un[e][c], lbv[c], ubv[c]) : un[e][c];
                     }
                 }
             }
