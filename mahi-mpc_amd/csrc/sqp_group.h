@@ -2611,6 +2611,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             });
         };
         bool jac_trial = false;
+        const FirstIterSwitch fsw = first_iter_switch(!XB && it == 0, c1, dJ);
         for (int ls = 0; ls < 30; ++ls) {
             double Jt = 0.0, ct = 0.0, lt = 0.0;
             jac_trial = FUSE_FWD && ls == 0;   // alpha = amax (1 without state bounds)
@@ -2622,7 +2623,7 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             const double phit = XB ? fma(mu, ct, fma(-2.0 * mub, lt, Jt)) : fma(mu, ct, Jt);
             const double noise = 1.0 + fabs(phi0);
             if (dphi >= -1e-11 * noise || phit <= phi0 + 1e-4 * alpha * dphi + 1e-13 * noise ||
-                (!XB && it == 0 && first_iter_filter_accepts(J0, c1, Jt, ct, dJ, alpha))) {
+                (!XB && it == 0 && first_iter_filter_accepts(J0, c1, Jt, ct, alpha, fsw))) {
                 accepted = true;
                 if (FUSE_FWD && jac_trial) {   // the next iteration starts after phase A
                     fwd_ready = true;

@@ -117,11 +117,45 @@ __device__ __forceinline__ double proj(double v, double lb, double ub) { return 
 // J_t <= J_0 - 1e-5 theta_0.  A nearly feasible first iterate (a warm start) whose step satisfies the switching
 // condition alpha (-dJ)^s_phi > theta_0^s_theta (s_phi = 2.3, s_theta = 1.1, delta = 1) is an f-type iteration:
 // the Armijo test alone decides it, as every later iteration.
+//
+// The one-expression form: the lane kernel's.  Its compiler hoists the two powers out of the search loop; both ways of
+// taking them off the path (below) were measured there and cost more than they save in kernels that spill registers:
+// stored in front of the loop, three more values across it, cfg#3 +3.4 %; formed at the trial, the control-bounded exo
+// kernels +7 % (192 -> 238 VGPR spills); a noinline helper for the rare path moves the spills of 19 of its 30 kernels.
 __device__ __forceinline__ bool first_iter_filter_accepts(double J0, double c0, double Jt, double ct, double dJ,
                                                           double alpha) {
     if (!(isfinite(Jt) && isfinite(ct))) return false;
     if (ct > 1e4 * fmax(1.0, c0)) return false;
     if (c0 <= 1e-4 * fmax(1.0, c0) && dJ < 0.0 && alpha * pow(-dJ, 2.3) > pow(c0, 1.1)) return false;
+    return ct <= (1.0 - 1e-5) * c0 || Jt <= J0 - 1e-5 * c0;
+}
+// The 16-lane and the condensed kernel: the two powers of (19) depend on the iterate and the step, not on the trial,
+// and only a nearly feasible first iterate with a descent step reads them.  first_iter_switch forms them once, in front
+// of the search loop, behind a branch that only such a lane takes (first: the SQP iteration is the first): a cold start
+// and every later iteration skip the two pow expansions (~455 instructions) instead of running them, hoisted and
+// speculated, in the iteration loop's straight-line code.  The empty asm makes pow's operands values of the branch, so
+// the expansions cannot be moved out of it or the branch be flattened into selects.  The trials read the stored
+// values.  Same pow, operands, comparison and order of tests as the one expression above.
+struct FirstIterSwitch {
+    bool near;          // theta_0 <= theta_min and dJ < 0: condition (19) decides
+    double pdj, pc0;    // (-dJ)^s_phi, theta_0^s_theta (read only where near)
+};
+__device__ __forceinline__ FirstIterSwitch first_iter_switch(bool first, double c0, double dJ) {
+    FirstIterSwitch s{false, 0.0, 0.0};
+    if (first && c0 <= 1e-4 * fmax(1.0, c0) && dJ < 0.0) {
+        double a = -dJ, b = c0;
+        asm volatile("" : "+v"(a), "+v"(b));
+        s.near = true;
+        s.pdj = pow(a, 2.3);
+        s.pc0 = pow(b, 1.1);
+    }
+    return s;
+}
+__device__ __forceinline__ bool first_iter_filter_accepts(double J0, double c0, double Jt, double ct, double alpha,
+                                                          const FirstIterSwitch& sw) {
+    if (!(isfinite(Jt) && isfinite(ct))) return false;
+    if (ct > 1e4 * fmax(1.0, c0)) return false;
+    if (sw.near && alpha * sw.pdj > sw.pc0) return false;
     return ct <= (1.0 - 1e-5) * c0 || Jt <= J0 - 1e-5 * c0;
 }
 // bound values of |b| >= 1e19 are infinite (IPOPT's convention); NaN marks a free control in hold fields.
@@ -1061,6 +1095,7 @@ __global__ __launch_bounds__(64, MMPC_WAVES_PER_SIMD) void sqp_wave_kernel(Solve
         const double dphi = dJ - mu * c1;
         double alpha = 1.0;
         bool accepted = false;
+        const FirstIterSwitch fsw = first_iter_switch(it == 0, c1, dJ);
         for (int ls = 0; ls < 30; ++ls) {
             double Jt = 0.0, ct = 0.0;
             if (lane < N) {
@@ -1109,7 +1144,7 @@ __global__ __launch_bounds__(64, MMPC_WAVES_PER_SIMD) void sqp_wave_kernel(Solve
             // of roundoff.  Without this the test compares noise and alpha collapses.
             const double noise = 1.0 + fabs(phi0);
             if (dphi >= -1e-11 * noise || phit <= phi0 + 1e-4 * alpha * dphi + 1e-13 * noise ||
-                (it == 0 && first_iter_filter_accepts(J0, c1, Jt, ct, dJ, alpha))) {
+                (it == 0 && first_iter_filter_accepts(J0, c1, Jt, ct, alpha, fsw))) {
                 accepted = true;
                 break;
             }
