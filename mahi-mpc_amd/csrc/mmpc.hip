@@ -742,8 +742,10 @@ size_t group_lds_instance_bytes(const mmpc_model_info& mi, int nq, const KernelV
     const int kc = mi.model_id == MMPC_MODEL_TWO_LINK_ARM ? mmpc::GroupLaneOps<TwoLinkArm>::doubles
                    : mi.model_id == MMPC_MODEL_EXO_ARM    ? mmpc::GroupLaneOps<ExoArm>::doubles
                                                           : 0;
+    // the head block of the gain record: the unbounded kernels of a model with a constant block
+    const int kh = kc > 0 && !v.ub && !v.xb ? mmpc::group_head_doubles(mi.num_x, mi.num_u) : 0;
     return static_cast<size_t>(mmpc::group_lds_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.ub,
-                                                       mi.is_linear != 0, v.xb, kc)) * sizeof(double);
+                                                       mi.is_linear != 0, v.xb, kc, kh)) * sizeof(double);
 }
 size_t group_lds_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
     return group_lds_instance_bytes(mi, nq, v) * kGroupsPerWave;

@@ -100,7 +100,7 @@ constexpr int kGroupLanes = 16;
 constexpr int kGroupsPerWave = 4;
 
 // LDS doubles per instance.  The hold targets (bounded solves) and the linear-mode block are only allocated
-// when used: at cfg#2 that keeps a 4-instance workgroup at 39,040 B (bounded: 40,960 B), so 4 workgroups (one per
+// when used: at cfg#2 that keeps a 4-instance workgroup at 40,384 B (bounded: 40,960 B), so 4 workgroups (one per
 // SIMD) fit a CU's 160 KB.  nq = kinematic rows of the model (sqp_lane.h a_mul); the stage blocks are h da/dq,
 // h da/dz, h da/du.  xb (the interior-point variant) adds nothing here since round 5: its per-stage z_l, z_u, Sigma,
 // b, z_u - z_l live in the HBM workspace (group_ws_doubles) -- in LDS they made 67.8 KB per workgroup at cfg#2, two
@@ -116,15 +116,20 @@ constexpr int kGroupsPerWave = 4;
 // operands (GroupLaneOps, below), [nx - 1 zeros | h | max(nx, nu) zeros].  Their serial sweeps read "this lane's row or
 // column of A_k" through a per-lane address and a per-lane stage stride: a lane with the role points into the stage
 // blocks, a q-lane's row h e_{nq+r} and the zero row of a lane without the role point here with stride 0 (cfg#2: 8
-// doubles, 39,040 B per workgroup).
+// doubles).
 __host__ __device__ constexpr int group_const_doubles(int nx, int nu) {
     return nx + nu < kGroupLanes ? nx + (nx > nu ? nx : nu) : 0;
 }
+// kh: doubles of the head block in front of the constant block, K_k | kff_k of stages 0 .. 2 ([3][nu][nx + nu + 1]) in
+// the unbounded kernels of a model with per-lane sweep operands: the step sweep opens with these rows a few hundred
+// cycles after the Riccati sweep's last stages formed them, and from the workspace they came back at the latency of
+// a load behind a store to the same line (cfg#2: 42 doubles, 40,384 B per workgroup).  The constant block stays last.
+__host__ __device__ constexpr int group_head_doubles(int nx, int nu) { return 3 * nu * (nx + nu + 1); }
 __host__ __device__ constexpr int group_lds_doubles(int nx, int nu, int nq, int N, bool bounded = true,
-                                                   bool linear = true, bool xb = false, int kc = 0) {
+                                                   bool linear = true, bool xb = false, int kc = 0, int kh = 0) {
     return N * (3 * nx + (nx - nq) * (nq + (nx - nq) + nu) + 2 * nu) + 3 * (N + 1) * nx + (bounded ? N * nu : 0) +
            (linear ? (nx - nq) * (nq + (nx - nq) + nu) + nx : 0) +
-           (N * ((nx - nq) * nu + nx) >= 2 * (nx - nq) * (nx - nq) ? 0 : 2 * (nx - nq) * (nx - nq)) + kc;
+           (N * ((nx - nq) * nu + nx) >= 2 * (nx - nq) * (nx - nq) ? 0 : 2 * (nx - nq) * (nx - nq)) + kh + kc;
 }
 // Models whose 16-lane kernels take the sweeps' lane operands through per-lane addresses, at the price of the constant
 // block: the 2-link arm (cfg#2, whose kernel is bound by the issue slots of one wave).  The other models keep the
@@ -150,6 +155,10 @@ __host__ __device__ constexpr int group_hess_doubles(int nx, int nu) { return nx
 // (x_{k+1} | u_k) after the W blocks, in place of the bounded solves' rows.
 // w_onchip (the unbounded exact-Hessian kernel of a model with a packed W record, WPack): the W blocks stay in LDS, so
 // the kernel strides instances by K | kff alone (420 doubles at cfg#2).
+// The unbounded kernels of a model with per-lane sweep operands keep K | kff of stages 0 .. 2 in LDS (group_lds_doubles,
+// kh) and leave those rows of the workspace unwritten; the control-bounded kernels (their LDS is at the budget), the
+// interior-point kernels and the exo and generated models keep the workspace path for all rows.  The layout and what
+// the host reserves are the same either way.
 // mehr (the xb variant under Mehrotra's predictor-corrector rule): the per-bound corrector terms of (x_{k+1} | u_k),
 // lower and upper, follow the xb fields; then per stage the record the predictor's Riccati sweep leaves for the
 // corrector's vector-only sweep: 2 + nu doubles per lane (P~_x c, the b-independent part of p~, L^-1 [H_wx | -R]) and
@@ -163,7 +172,8 @@ __host__ __device__ constexpr int group_ws_doubles(int nx, int nu, int N, bool b
 // the cfg#2 shape (2-link arm, N = 30, unbounded): four instances per workgroup within 40,960 B of LDS, so that four
 // workgroups (one per SIMD) fit a CU -- the on-chip W record lives in arrays that are dead while it is alive and adds
 // nothing to this
-static_assert(kGroupsPerWave * group_lds_doubles(4, 2, 2, 30, false, false, false, GroupLaneOps<TwoLinkArm>::doubles) * 8 <= 40960,
+static_assert(kGroupsPerWave * group_lds_doubles(4, 2, 2, 30, false, false, false, GroupLaneOps<TwoLinkArm>::doubles,
+                                                 group_head_doubles(4, 2)) * 8 <= 40960,
               "cfg#2 LDS budget");
 
 struct GroupWork {
@@ -375,7 +385,9 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // ---- LDS views of this instance ----
     // constant block of the per-lane sweep operands (LOPS, below): the models with GroupLaneOps, lane-distributed path
     constexpr int KC = NX + NU < kGroupLanes ? GroupLaneOps<Model>::doubles : 0;
-    double* const sX = shm + gi * group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC);  // [N+1][NX]
+    // head block of the gain record (group_lds_doubles): the unbounded kernels of those models
+    constexpr int KH = (KC > 0 && !BOUNDED && !XB) ? group_head_doubles(NX, NU) : 0;
+    double* const sX = shm + gi * group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC, KH);  // [N+1][NX]
     // sD | sDX | sDU are contiguous: between the W pass and the step sweep of an iteration all three are dead (d / lam
     // in sD: the W pass is its last reader; sDX, sDU: the previous step, consumed by the update) and, on the on-chip W
     // path (WLDS), sD + NX .. holds the packed W records (sW) -- d_0 = 0 in sD[0..NX) stays
@@ -561,7 +573,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
     // blends fma(lad, v, hrow) / lad v + lqd v' delivered (1 v + 0, or 0 v + h with v finite), without the FP64
     // instructions -- the same idiom as the W slots (wrow): per-lane addresses, never a select of a loaded value.
     constexpr bool LOPS = KC > 0;
-    double* const sKc = sX + group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC) - KC;
+    double* const sKc = sX + group_lds_doubles(NX, NU, NQ, N, BOUNDED, p.is_linear != 0, XB, KC, KH) - KC;
+    [[maybe_unused]] double* const sKh = sKc - KH;   // [3][NU][NS+1]: K_k | kff_k of stages 0 .. 2
     // (the addresses are LDS pointers, so that the base of the dynamic LDS is added here once and not at every load)
     using LdsB = const __attribute__((address_space(3))) char*;
     using LdsD = const __attribute__((address_space(3))) double*;
@@ -1489,29 +1502,69 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 for (int j = 0; j < NX; ++j) Prow[j] = fma(dgx[j], sgN, Prow[j]);
                 pvr = fma(lxm, bbN, pvr);
             }
-            // (the sweep is issue-bound: its LDS operands are read in place; a prefetch buffer spills to AGPRs)
+            // The stage's first FMAs (T, mv) need P~'s row, which is in registers, and h da/du and c of the stage: LDS
+            // returns a wave's reads in order and the wave has nothing else to issue at the stage's top, so whatever
+            // is queued in front of those two is waited for in full.  LOPS: the two are handed over from the stage
+            // before (Hb, loaded in the middle of that stage's P~ update, as the W row one stage ahead), and the stage's
+            // other operands are read in place in the order of first use, those of colA / at_mul last.  (A buffer for
+            // all of a stage's operands spills to AGPRs; the sweep is otherwise bound by issue slots.)
+            struct Hb {
+                double fu[FU], c[NX];
+            };
+            Hb h0;
+            auto load_head = [&](int k, Hb& b) {
+#pragma unroll
+                for (int i = 0; i < FU; ++i) b.fu[i] = sFu[k * FU + i];
+#pragma unroll
+                for (int q = 0; q < NX; ++q) b.c[q] = sC[k * NX + q];
+            };
+            if constexpr (LOPS) load_head(N - 1, h0);
             // stage k; LAST = (k == 0), peeled so that the stages k >= 1 carry no k == 0 selects or branches
-            auto stage = [&](int k, auto last_c, Wb& wb) {
-                constexpr bool LAST = decltype(last_c)::value;
+            // HEADK: a stage k <= 2 of a kernel with the head block, which takes its K | kff columns
+            auto stage = [&](int k, auto last_c, auto head_c, Wb& wb, Hb& hb) {
+                constexpr bool LAST = decltype(last_c)::value, HEADK = decltype(head_c)::value;
 #if defined(MMPC_PHASE_TIMING) && defined(MMPC_PHASE_STAGES)
-                if (gl == 0 && blockIdx.x < kPhaseWavePhases && k < 32)
-                    g_mmpc_phase_cycles[kPhaseStageLog + 128 * blockIdx.x + 32 * gi + k] = __builtin_amdgcn_s_memtime();
+                const unsigned long long st_top = __builtin_amdgcn_s_memtime();
+                __builtin_amdgcn_sched_barrier(0);
 #endif
                 double hFq[SQ], hFqd[FD], hFu[FU], cc[NX], u[NU], um[NU], acol[NA];
+                if constexpr (!LOPS) {
 #pragma unroll
-                for (int i = 0; i < FQ; ++i) hFq[i] = sFq[k * FQ + i];
+                    for (int i = 0; i < FQ; ++i) hFq[i] = sFq[k * FQ + i];
 #pragma unroll
-                for (int i = 0; i < FD; ++i) hFqd[i] = sFqd[k * FD + i];
+                    for (int i = 0; i < FD; ++i) hFqd[i] = sFqd[k * FD + i];
+                    load_head(k, hb);
+                }
 #pragma unroll
-                for (int i = 0; i < FU; ++i) hFu[i] = sFu[k * FU + i];
+                for (int i = 0; i < FU; ++i) hFu[i] = hb.fu[i];
 #pragma unroll
-                for (int q = 0; q < NX; ++q) cc[q] = sC[k * NX + q];
+                for (int q = 0; q < NX; ++q) cc[q] = hb.c[q];
+#if defined(MMPC_PHASE_TIMING) && defined(MMPC_PHASE_STAGES)
+                // the stamp behind the arrival of the operands of T and mv (s_memtime's own result needs lgkmcnt(0):
+                // in the order of the other models it also waits for the reads queued behind them)
+#pragma unroll
+                for (int i = 0; i < FU; ++i) asm volatile("" ::"v"(hFu[i]));
+#pragma unroll
+                for (int q = 0; q < NX; ++q) asm volatile("" ::"v"(cc[q]));
+                __builtin_amdgcn_sched_barrier(0);
+                if (gl == 0 && blockIdx.x < kPhaseWavePhases && k < 32) {
+                    g_mmpc_phase_cycles[kPhaseStageLog + 128 * blockIdx.x + 32 * gi + k] = st_top;
+                    g_mmpc_phase_cycles[kPhaseWaitLog + 128 * blockIdx.x + 32 * gi + k] = __builtin_amdgcn_s_memtime();
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
                 for (int c = 0; c < NU; ++c) {
                     u[c] = sU[k * NU + c];
                     um[c] = LAST ? up[c] : sU[(k - 1) * NU + c];
                 }
                 load_acol(k, jcol, acol);
+                if constexpr (LOPS) {
+#pragma unroll
+                    for (int i = 0; i < FQ; ++i) hFq[i] = sFq[k * FQ + i];
+#pragma unroll
+                    for (int i = 0; i < FD; ++i) hFqd[i] = sFqd[k * FD + i];
+                }
                 // XB: the barrier pieces of this stage (u_k) and of x_k (stage k-1), loaded with the stage operands:
                 // read at their uses, deep in the stage, their HBM latency was exposed
                 double xsgu[XB ? NU : 1], xbbu[XB ? NU : 1], xsgx = 0.0, xbbx = 0.0;
@@ -1779,7 +1832,8 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 {
                     const int col = r < NS ? r : NS;
 #pragma unroll
-                    for (int a = 0; a < NU; ++a) wK[(k * NU + a) * (NS + 1) + col] = -(r < NS ? Kcol[a] : kff[a]);
+                    for (int a = 0; a < NU; ++a)
+                        (HEADK ? sKh : wK)[(k * NU + a) * (NS + 1) + col] = -(r < NS ? Kcol[a] : kff[a]);
                 }
                 if constexpr (LAST) return;
                 // A^T P_xx A (row r) from the broadcast P_xx, p~_x = A^T mv + Q (x_k - r_{k-1})
@@ -1800,6 +1854,14 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     Ur[j] = colA(Prow[j], acol, pc);
                 }
                 at_mul<NQ, NA, double>(h, hFq, hFqd, Ur, Pn);
+                // the next stage's h da/du and c: T, mv, H_ww and h_w of this stage are formed, so the buffer is free, and
+                // the rest of the P~ update (some 60 instructions) covers the reads.  Left alone, the scheduler sinks
+                // them to their uses at the next stage's top; the barrier further up in the stage (in front of the
+                // P~ update, or of Y) made the unbounded exact kernel spill.
+                if constexpr (LOPS) {
+                    load_head(k - 1, hb);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 // x-lanes A^T mv + Q (x_k - r_{k-1}), u-lanes -R (u_k - u_{k-1}), idle lanes 0 -- blended with the
                 // lane-role factor (Rr = 0 off the u-lanes) instead of a branch
                 double pn = fma(-Rr, duu, lxm * fma(Qr, exr, colA(mv, acol, mvb)));
@@ -1857,22 +1919,41 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
             // the control-bounded sweep one stage per trip (its hold logic and relaxation rows fill the registers: two
             // stages in flight spilled to scratch inside the loop)
             using F_ = std::false_type;
+            using T_ = std::true_type;
             if constexpr (BOUNDED || (XB && EXACT)) {
-                for (int k = N - 1; k >= 1; --k) stage(k, F_{}, w0);
-                stage(0, std::true_type{}, w0);
-            } else if ((N - 1) & 1) {
-                stage(N - 1, F_{}, w0);
-                for (int k = N - 2; k >= 2; k -= 2) {
-                    stage(k, F_{}, w0);
-                    stage(k - 1, F_{}, w0);
+                for (int k = N - 1; k >= 1; --k) stage(k, F_{}, F_{}, w0, h0);
+                stage(0, T_{}, F_{}, w0, h0);
+            } else if constexpr (KH > 0) {
+                // head block: the pair loop ends at stage 3 (an odd count of stages N - 1 .. 3 peels stage N - 1), and
+                // the stages 2, 1 (one more pair body) and 0 that store there follow as straight-line code -- a store
+                // address chosen per stage inside the loop would cost every stage what these three save.  (Stages
+                // 2 and 1 each under a test of their own made the exact kernel spill four registers.)
+                int k = N - 1;
+                if (N >= 4 && ((N - 3) & 1)) stage(k--, F_{}, F_{}, w0, h0);
+                for (; k >= 4; k -= 2) {
+                    stage(k, F_{}, F_{}, w0, h0);
+                    stage(k - 1, F_{}, F_{}, w0, h0);
                 }
-                stage(0, std::true_type{}, w0);
+                if (N >= 3) {
+                    stage(2, F_{}, T_{}, w0, h0);
+                    stage(1, F_{}, T_{}, w0, h0);
+                } else if (N == 2) {
+                    stage(1, F_{}, T_{}, w0, h0);
+                }
+                stage(0, T_{}, T_{}, w0, h0);
+            } else if ((N - 1) & 1) {
+                stage(N - 1, F_{}, F_{}, w0, h0);
+                for (int k = N - 2; k >= 2; k -= 2) {
+                    stage(k, F_{}, F_{}, w0, h0);
+                    stage(k - 1, F_{}, F_{}, w0, h0);
+                }
+                stage(0, T_{}, F_{}, w0, h0);
             } else {
                 for (int k = N - 1; k >= 2; k -= 2) {
-                    stage(k, F_{}, w0);
-                    stage(k - 1, F_{}, w0);
+                    stage(k, F_{}, F_{}, w0, h0);
+                    stage(k - 1, F_{}, F_{}, w0, h0);
                 }
-                stage(0, std::true_type{}, w0);
+                stage(0, T_{}, F_{}, w0, h0);
             }
         };
         // MEHR corrector: the vector part (p~, kff) of the Riccati recursion for the barrier gradient now in sBb, on the
@@ -2153,6 +2234,10 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 constexpr bool RUN = MIRROR;   // running addresses, unmasked stores, no clamped prefetch (below)
                 double sr = 0.0;
+#if defined(MMPC_PHASE_TIMING) && defined(MMPC_PHASE_STAGES)
+                if (gl == 0 && blockIdx.x < kPhaseWavePhases)
+                    g_mmpc_phase_cycles[kPhaseStepLog + 8 * blockIdx.x + 2 * gi] = __builtin_amdgcn_s_memtime();
+#endif
                 if (RUN || lx) sDX[rx] = 0.0;
                 constexpr int NK = NS + 1;
                 const double* const Kp = wK + ru * NK;   // row ru of K_k | kff_k at Kp + k NU NK
@@ -2181,9 +2266,10 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                 using GlbD = const __attribute__((address_space(1))) double*;   // (stays a global load behind the pin)
                 [[maybe_unused]] GlbD jK = (GlbD)Kp;
                 [[maybe_unused]] GlbD jR = (GlbD)Rp;
-                [[maybe_unused]] auto refill = [&](Ops& o) {   // the next stage in order
+                // (hs: -1, or the stage 0 .. 2 whose K row the head block holds -- the opening's refills)
+                [[maybe_unused]] auto refill = [&](Ops& o, int hs = -1) {   // the next stage in order
 #pragma unroll
-                    for (int j = 0; j < NK; ++j) o.K[j] = jK[j];
+                    for (int j = 0; j < NK; ++j) o.K[j] = (KH > 0 && hs >= 0) ? sKh[(hs * NU + ru) * NK + j] : jK[j];
 #pragma unroll
                     for (int s2 = 0; s2 < NQ; ++s2) o.a[s2] = lds(ja + 8 * s2);
 #pragma unroll
@@ -2277,6 +2363,11 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                             }
                         }
                     }
+#if defined(MMPC_PHASE_TIMING) && defined(MMPC_PHASE_STAGES)
+                    asm volatile("" ::"v"(sr), "v"(ad));
+                    if (k == 0 && gl == 0 && blockIdx.x < kPhaseWavePhases)
+                        g_mmpc_phase_cycles[kPhaseStepLog + 8 * blockIdx.x + 2 * gi + 1] = __builtin_amdgcn_s_memtime();
+#endif
                     if constexpr (RUN) {
                         if (more) {
                             refill(o);
@@ -2298,12 +2389,26 @@ __global__ __launch_bounds__(64) void sqp_group_kernel(SolveParams p, GroupWork 
                     // or two left over follow it; the last three stages run without a refill, from the buffers the
                     // rotation has reached.  The opening loads of a horizon shorter than three read its last stage
                     // again (values never used) instead of moving on.
-                    refill(o0);
-                    if (N > 1) advance();
-                    refill(o1);
-                    if (N > 2) advance();
-                    refill(o2);
-                    advance();
+                    // With the head block (KH) the opening's K rows are LDS reads, under one uniform test for the
+                    // horizons that have three stages (the form with a test between the refills makes the exact kernel
+                    // spill two registers); the K pointer runs along, so that the first refill of a stage finds row 3
+                    // of the workspace.  Where the K rows come from the workspace the test sits between the refills:
+                    // the uniform form measured slower there.
+                    if (KH == 0 || N < 3) {
+                        refill(o0, 0);
+                        if (N > 1) advance();
+                        refill(o1, N > 1 ? 1 : 0);
+                        if (N > 2) advance();
+                        refill(o2, N > 2 ? 2 : N - 1);
+                        advance();
+                    } else {
+                        refill(o0, 0);
+                        advance();
+                        refill(o1, 1);
+                        advance();
+                        refill(o2, 2);
+                        advance();
+                    }
                     int k = 0;
                     for (; k + 5 < N; k += 3) {
                         stage(k, o0, true);

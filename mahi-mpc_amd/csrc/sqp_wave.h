@@ -455,8 +455,14 @@ constexpr int kPhaseStageLog = 16 + 2 * kPhaseWaveLog + 40 * kPhaseWavePhases;
 // channel and stalled the memory operations of the waves still running (round 6)
 constexpr int kPhaseSpread = 64;
 constexpr int kPhaseSpreadBase = kPhaseStageLog + 128 * kPhaseWavePhases;
-constexpr int kPhaseSlots = kPhaseSpreadBase + 32 * kPhaseSpread;
-// the table every unit carries: all of the above (1.46 MB) in the timing build; otherwise nothing writes it and 16 slots
+// and (-DMMPC_PHASE_STAGES, 16-lane kernels) behind the spread copies, for the first 1024 waves:
+//   kPhaseWaitLog + 128 * blockIdx.x + 32 * group + stage: the stamp after the first operand wait of that Riccati stage
+//     (its stage-top stamp is the one at kPhaseStageLog), stages < 32, the last sweep
+//   kPhaseStepLog + 8 * blockIdx.x + 2 * group + {0, 1}: the top of the last step sweep and the end of its stage 0
+constexpr int kPhaseWaitLog = kPhaseSpreadBase + 32 * kPhaseSpread;
+constexpr int kPhaseStepLog = kPhaseWaitLog + 128 * kPhaseWavePhases;
+constexpr int kPhaseSlots = kPhaseStepLog + 8 * kPhaseWavePhases;
+// the table every unit carries: all of the above (2.57 MB) in the timing build; otherwise nothing writes it and 16 slots
 // are there for mmpc_debug_phase_cycles to read as zeros
 #ifdef MMPC_PHASE_TIMING
 constexpr int kPhaseTableSlots = kPhaseSlots;

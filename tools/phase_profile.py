@@ -61,10 +61,16 @@ ub = None if a.u_bound is None else torch.full((nu,), a.u_bound, **f)
 it = torch.zeros(B, dtype=torch.int32, device="cuda")
 s.solve_batch(B, x0, up, tr, w, V, None, it, None, u_lb=lb, u_ub=ub)
 torch.cuda.synchronize()
-NSLOT = 16 + 2 * 4096 + 40 * 1024 + 128 * 1024
+# (sqp_wave.h: the per-stage log, the spread copies, then -- a -DMMPC_PHASE_STAGES build fills them -- the stamps after
+# each Riccati stage's first operand wait and the two stamps of the step sweep's opening)
+STAGE_LOG = 16 + 2 * 4096 + 40 * 1024
+WAIT_LOG = STAGE_LOG + 128 * 1024 + 32 * 64
+STEP_LOG = WAIT_LOG + 128 * 1024
+NSLOT = STEP_LOG + 8 * 1024
 L.mmpc_debug_phase_table.argtypes = [C.c_void_p, C.c_int, C.c_int]
 buf = (C.c_ulonglong * NSLOT)()
-L.mmpc_debug_phase_table(buf, NSLOT, 1)
+if L.mmpc_debug_phase_table(buf, NSLOT, 1) != 0:
+    raise SystemExit("not a timing build (lib/libmmpc_timing.so): " + L.mmpc_last_error().decode())
 V.zero_()
 s.solve_batch(B, x0, up, tr, w, V, None, it, None, u_lb=lb, u_ub=ub)
 torch.cuda.synchronize()
@@ -114,4 +120,20 @@ if len(dur) and int(waves) == nw:
     out["mean_us_by_wave_max_iters"] = {
         int(m): [float(dur[wm == m].mean()), float(ghz[wm == m].mean()), int((wm == m).sum())]
         for m in np.unique(wm)}
+if ksolver == 3 and N <= 32 and any(buf[WAIT_LOG:WAIT_LOG + 32]):
+    # waves whose four groups all ran the last sweep in the same iteration: the same stamps in all four groups
+    nb = min(nw, 1024)
+    top = np.array(buf[STAGE_LOG:STAGE_LOG + 128 * nb], dtype=np.int64).reshape(nb, 4, 32)[:, 0, :N]
+    wt = np.array(buf[WAIT_LOG:WAIT_LOG + 128 * nb], dtype=np.int64).reshape(nb, 4, 32)[:, 0, :N]
+    st = np.array(buf[STEP_LOG:STEP_LOG + 8 * nb], dtype=np.int64).reshape(nb, 4, 2)[:, 0]
+    ok = (top > 0).all(1) & (wt > top).all(1)
+    first = (wt - top)[ok]            # [waves][stage]: stage top -> operands of T and mv have arrived
+    stage = -np.diff(top[ok], axis=1)  # top of stage k - top of stage k + 1 = the length of stage k + 1
+    op = (st[:, 1] - st[:, 0])[(st[:, 0] > 0) & (st[:, 1] > st[:, 0])]
+    pc = lambda a: {str(q): float(np.percentile(a, q)) for q in (10, 50, 90)}   # noqa: E731
+    out["riccati_first_wait_cycles"] = {"waves": int(ok.sum()), "inner_stages": pc(first[:, 1:N - 1]),
+                                        "first_stage(N-1)": pc(first[:, N - 1]), "last_stage(0)": pc(first[:, 0]),
+                                        "median_by_stage": np.median(first, 0).tolist()}
+    out["riccati_stage_cycles"] = pc(stage)
+    out["step_opening_cycles(top..end of stage 0)"] = dict(pc(op), waves=int(len(op)))
 print(json.dumps(out, indent=1))
