@@ -727,7 +727,7 @@ mmpc_model_info with_horizon(const mmpc_model_info& mi, int N) {
 }
 
 // Sizes by key (kernel_variant.h): the kernels stride their LDS and workspace by their own template flags (sqp_group.h
-// group_lds_doubles / group_ws_doubles, sqp_lane.h lane_ws_doubles), and these are the host's only calls of those
+// group_lds / group_ws_doubles, sqp_lane.h lane_ws_doubles), and these are the host's only calls of those
 // functions, each flag taken from the key's member of the same meaning.
 // per-instance doubles of the 16-lane kernel's workspace (the host never counts on the on-chip W record)
 int group_ws_doubles(const mmpc_model_info& mi, const KernelVariant& v) {
@@ -744,8 +744,8 @@ size_t group_lds_instance_bytes(const mmpc_model_info& mi, int nq, const KernelV
                                                           : 0;
     // the head block of the gain record: the unbounded kernels of a model with a constant block
     const int kh = kc > 0 && !v.ub && !v.xb ? mmpc::group_head_doubles(mi.num_x, mi.num_u) : 0;
-    return static_cast<size_t>(mmpc::group_lds_doubles(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.ub,
-                                                       mi.is_linear != 0, v.xb, kc, kh)) * sizeof(double);
+    return static_cast<size_t>(mmpc::group_lds(mi.num_x, mi.num_u, nq, mi.num_shooting_nodes, v.ub, mi.is_linear != 0,
+                                               kc, kh).doubles) * sizeof(double);
 }
 size_t group_lds_bytes(const mmpc_model_info& mi, int nq, const KernelVariant& v) {
     return group_lds_instance_bytes(mi, nq, v) * kGroupsPerWave;

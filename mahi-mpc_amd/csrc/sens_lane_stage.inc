@@ -1,8 +1,8 @@
 // sens_lane_stage.inc -- the text the sensitivity kernels share: the instance prologue and the backward stage of the
 // one-lane-per-instance sweeps (gain_sweep.h, adjoint_sweep.h; the recursion is stated at the top of gain_sweep.h).
 //
-// This is kernel text, not a header: it is compiled into each kernel from here, the way sqp_group.h compiles its body
-// into two kernels, because a __device__ function holding the stage changes the register allocation, the scratch and
+// This is kernel text, not a header: it is compiled into each kernel from here, the way sqp_group.h compiles
+// sqp_group_body.inc into its three kernels, because a __device__ function holding the stage changes the register allocation, the scratch and
 // in some instantiations the FP64 operation counts of every kernel that calls it (DESIGN.md 3j).  Set MMPC_SENS_PART
 // and include the file inside the kernel; the file undefines the macro again.
 //

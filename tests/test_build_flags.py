@@ -47,6 +47,29 @@ def test_two_link_group_kernels_only_in_their_unit():
     assert "sqp_group_kernel<TwoLinkArm" in grp
 
 
+def _var(makefile, name):
+    return re.search(r"^%s := (.*)$" % name, open(makefile).read(), re.M).group(1).split()
+
+
+def test_makefiles_list_every_included_kernel_file():
+    """Every csrc/*.h and csrc/*.inc that mmpc.hip or group_two_link.hip reaches through #include "...", transitively,
+    is a prerequisite of the kernel units (HDR), and every csrc/*.inc one of the generated models' libraries (KSRC): a
+    file missing there is edited without anything being rebuilt"""
+    csrc = os.path.join(AMD, "csrc")
+    seen, todo = set(), ["mmpc.hip", "group_two_link.hip"]
+    while todo:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, todo.pop())).read(), re.M):
+            if inc not in seen and "/" not in inc and os.path.exists(os.path.join(csrc, inc)):
+                seen.add(inc)
+                todo.append(inc)
+    incs = {f for f in os.listdir(csrc) if f.endswith(".inc")}
+    assert incs and incs <= seen, incs - seen   # no stray kernel text
+    hdr = set(_var(os.path.join(AMD, "Makefile"), "HDR"))
+    assert {"csrc/" + f for f in seen} <= hdr, sorted({"csrc/" + f for f in seen} - hdr)
+    ksrc = set(_var(os.path.join(AMD, "host", "Makefile"), "KSRC"))
+    assert {"../csrc/" + f for f in incs} <= ksrc, sorted({"../csrc/" + f for f in incs} - ksrc)
+
+
 def test_generated_model_libraries_use_the_basic_allocator():
     """ModelGenerator::compile_model builds both kernel units of a user model with the basic SGPR allocator"""
     src = open(os.path.join(AMD, "host", "src", "ModelGenerator.cpp")).read()
