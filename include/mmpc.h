@@ -531,6 +531,84 @@ int mmpc_solve_jvp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
                               const double* dtraj, const double* dweights, int32_t hessian, double* dV, double* du0,
                               int32_t* jvp_status);
 
+/* ---- real-time iteration: a prepare launch and a feedback launch per tick (additive to ABI 6) ----
+ * One full-step SQP iteration at a plan V^ that is NOT a solution -- typically the previous solution shifted by one
+ * stage -- split in two.  The preparation runs while the plant still moves towards the next sampling instant: it
+ * linearises at V^, forms the gradient and the defects, runs the backward Riccati sweep and stores the stage records.
+ * The feedback runs when x_0 is measured: one forward sweep over the records, no model, no factor.  (The solve JVP
+ * above is the sensitivity of a converged plan: its right-hand side has no gradient residual and no defects.)
+ *
+ * Definition.  Notation of the gain, VJP and JVP comments, all at V^ = (x^_0, u^_0, x^_1, .., x^_N).  u_prev is the
+ * control in force over the coming interval; it is known at prepare time.  With c_k = F(x^_k, u^_k) - x^_{k+1} the
+ * step dV solves
+ *   min 1/2 dV^T H dV + grad J(V^)^T dV
+ *   s.t. dx_{k+1} = A_k dx_k + B_k du_k + c_k,   dx_0 = x0_meas - x^_0,   du_k = 0 on held controls,
+ * H the Hessian of the Lagrangian (S_k, + W_k under EXACT, the -2R couplings) with the multipliers of the gain
+ * recursion (lam_{N-1} = 0, lam_{k-1} = A_k^T nu_k, nu_k = 2 Q e_k + lam_k).  On the feasible set grad J^T dV and
+ * grad L^T dV differ by a constant, and with these multipliers the x rows of grad L vanish; the u rows are
+ *   r_{u,k} = B_k^T nu_k + 2R((u_k - u_{k-1}) - (u_{k+1} - u_k)) + 2Rm u_k,
+ * u_{-1} = u_prev, the (u_{k+1} - u_k) term absent at k = N-1.  The held mask is the sensitivities': bit-equal to a
+ * finite bound, or k < n_pin.
+ * Recursion, with the cost-to-go written 1/2 s^T P_k s - p_k^T s (p has the sign of the JVP's p, so the recursion is the
+ * JVP's with rho_k = -(0; r_{u,k}) - C_k^T P_{k+1} (c_k; 0)): backward over k = N-1..0 from P_N = 0, p_N = 0, with
+ * P_k, M_*, G_k exactly as in the gains,
+ *   q = C_k^T (p_{k+1} - P_{k+1} (c_k; 0)) - (0; r_{u,k});  q_u of a held control is 0;
+ *   kff_k = M_uu^-1 q_u;  p_k = (q_x; 0) + G_k^T q_u.
+ * Forward from s_0 = (dx_0; 0):  du_k = G_k s_k + kff_k,  dx_{k+1} = A_k dx_k + B_k du_k + c_k,  s_{k+1} = (dx_{k+1}; du_k).
+ * Control box: with u_lb / u_ub given to the feedback call the forward sweep forms u_k+ = clamp(u^_k + du_k, lb, ub)
+ * and propagates du_k = u_k+ - u^_k (the projected forward pass of box-iLQR); every returned control is inside the box
+ * bit for bit.  A du_k that is exactly 0 -- a held control has a zero row of G_k and kff 0 -- leaves the control as it
+ * is, so a pinned control keeps its value whatever the box.
+ * Output: V_inout = V^ + dV with V[0:nx] bit for bit x0_meas; u0_out = u_0+, bit for bit V_inout's u_0; step_inf =
+ * max |V_inout - V^| over the entries as stored.  The step is the full step: no line search.  Per instance:
+ *   status 0   as asked
+ *          1   Gauss-Newton fallback: a pivot <= 0 or non-finite under EXACT redoes the whole preparation of the instance
+ *              with Gauss-Newton
+ *          2   failed: decided at prepare time for a non-finite input or a step that is not positive definite even with
+ *              Gauss-Newton, at feedback time for a non-finite x0_meas or a non-finite step.  V_inout is left bit for
+ *              bit as given, u0_out is the plan's own u^_0, step_inf is +inf (no step was taken; a caller that
+ *              thresholds step_inf alone falls back to a full solve); neighbours in the batch are untouched.
+ *   prep_status reports 0 / 1 / 2 as far as the preparation knows; the feedback call's status carries it on.
+ *
+ * Arguments.  V, u_prev, traj, weights / weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian: as for
+ * mmpc_solve_jvp_batch, validation (codes and the argument names in mmpc_last_error) included.  x0_meas [B][nx];
+ * V_inout [B][NV], holding the plan the preparation was given; u0_out [B][nu], step_inf [B], status [B], prep_status [B]
+ * may each be NULL.  u0_out, step_inf and status may point into mmpc_host_alloc memory, as for mmpc_solve_batch_u0.
+ * The feedback call takes no model inputs: the preparation's status, n_pin and the held mask reach it through the
+ * workspace.  Its u_lb / u_ub / bounds_stride are the box of the clamp (normally the preparation's).
+ *   workspace    caller-provided DEVICE memory of mmpc_rti_workspace_bytes(h, B) bytes, K = nx + nu:
+ *                  ceil(B / 64) * 64 * ((N K (K + 1) + NV) * 8 + 4)  bytes:
+ *                per stage the record G_k | kff_k (nu rows of K + 1) and A_k | B_k | c_k (nx rows of K + 1), K (K + 1)
+ *                doubles (156 N per instance for the exo), lane-interleaved in blocks of 64 instances in the layout of
+ *                the VJP's record; then NV doubles per instance in which the feedback launch keeps the plan entries it
+ *                overwrites, so that a failed step can be undone; then one int32 status word per instance.  The stored
+ *                A | B | c are the price of a feedback sweep that evaluates no model.
+ *                NULL or smaller than the query: MMPC_ERR_INVALID_ARG naming `workspace` / `workspace_bytes`.
+ * A feedback call on a workspace that no prepare call of the same handle and B has filled, or with a V_inout that is
+ * not the plan that prepare call was given, is the caller's error and is not detected.  One preparation serves one
+ * feedback call on that plan.
+ * Refused with MMPC_ERR_UNSUPPORTED: a linear-mode model; a handle with any finite state bound, whether the sensitivity
+ * barrier is on or off (a one-step interior point is not computed).  Everything is checked from the arguments alone
+ * before any device call; B = 0 is a no-op success.
+ * mmpc_rti_prepare_batch and mmpc_rti_feedback_batch take DEVICE pointers; each is one stream-ordered launch on
+ * `stream` that never synchronises and never allocates (the handle's workspace is not used; mmpc_reserve_workspace's
+ * sizes are unchanged), so both can be captured in a hipGraph.  mmpc_rti_step_batch_host takes host pointers, runs
+ * preparation and feedback back to back, brings its own workspace and is synchronous.  State-bounded handles,
+ * inequality constraints beyond the clamp, multi-device and RCCL entries, a 16-lane kernel, globalisation: out of
+ * scope. */
+int mmpc_rti_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes);
+int mmpc_rti_prepare_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                           const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                           int64_t bounds_stride, int32_t n_pin, int32_t hessian, int32_t* prep_status,
+                           void* workspace, uint64_t workspace_bytes, void* stream);
+int mmpc_rti_feedback_batch(mmpc_handle* h, int64_t B, const double* x0_meas, const double* u_lb, const double* u_ub,
+                            int64_t bounds_stride, double* V_inout, double* u0_out, double* step_inf, int32_t* status,
+                            void* workspace, uint64_t workspace_bytes, void* stream);
+int mmpc_rti_step_batch_host(mmpc_handle* h, int64_t B, double* V_inout, const double* x0_meas, const double* u_prev,
+                             const double* traj, const double* weights, int64_t weights_stride, const double* u_lb,
+                             const double* u_ub, int64_t bounds_stride, int32_t n_pin, int32_t hessian, double* u0_out,
+                             double* step_inf, int32_t* status);
+
 /* ---- feedback gains and solve VJP of a state-bounded handle: the sensitivity barrier (additive to ABI 6) ----
  * A state-bounded solve is an interior-point solve: the V it returns lies strictly inside every bound, near the
  * central path of its last barrier value.  Its sensitivity is the recursion of the two definitions above with the

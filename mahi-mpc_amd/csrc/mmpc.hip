@@ -26,6 +26,7 @@
 #include "json_lite.h"
 #include "adjoint_sweep.h"
 #include "tangent_sweep.h"
+#include "rti_sweep.h"
 #include "gain_sweep.h"
 #include "group_launch.h"
 #include "lane_launch.h"
@@ -1656,6 +1657,120 @@ int launch_jvp(mmpc_handle* h, const JvpArgs& a, bool exact, const XbTail& xb) {
     });
 }
 
+// ---- real-time iteration (mmpc_rti_prepare_batch / mmpc_rti_feedback_batch; rti_sweep.h) ----
+struct RtiArgs : SensArgs {   // the preparation's arguments are the head; the rest is the feedback launch's
+    const double* x0_meas = nullptr;
+    double *V_inout = nullptr, *u0 = nullptr, *step_inf = nullptr;
+    int32_t* fb_status = nullptr;
+    void* workspace = nullptr;
+    uint64_t workspace_bytes = 0;
+};
+uint64_t rti_ws_bytes(const mmpc_model_info& mi, int64_t B) {
+    return rti_workspace_bytes(mi.num_x, mi.num_u, mi.num_shooting_nodes, B);
+}
+// the two refusals every RTI entry shares, before the sensitivity barrier is looked at: a state-bounded handle is
+// refused with the barrier on or off
+int check_rti_handle(mmpc_handle* h) {
+    if (h->info.is_linear)
+        return fail(MMPC_ERR_UNSUPPORTED, "real-time iteration is not available for a linear-mode model");
+    std::lock_guard<std::mutex> lk(h->xb_mu);
+    if (h->x_bounded)
+        return fail(MMPC_ERR_UNSUPPORTED, "real-time iteration is not available with finite state bounds, whether the "
+                                          "sensitivity barrier is on or off (a one-step interior point is not computed)");
+    return MMPC_OK;
+}
+int check_rti_workspace(mmpc_handle* h, const RtiArgs& a) {
+    const uint64_t need = rti_ws_bytes(h->info, a.B);
+    if (!a.workspace)
+        return fail(MMPC_ERR_INVALID_ARG,
+                    "workspace is NULL: needs " + std::to_string(need) + " bytes (mmpc_rti_workspace_bytes)");
+    if (a.workspace_bytes < need)
+        return fail(MMPC_ERR_INVALID_ARG, "workspace_bytes is " + std::to_string(a.workspace_bytes) + ", needs " +
+                                              std::to_string(need) + " (mmpc_rti_workspace_bytes)");
+    return MMPC_OK;
+}
+// The one check of a preparation's arguments: check_sens_args with the RTI refusals (the host entry brings its own
+// workspace and passes check_workspace = false).
+int check_rti_prepare_args(mmpc_handle* h, const RtiArgs& a, bool check_workspace, bool* exact) {
+    XbTail xb;
+    const int rc = check_sens_args(h, a, "real-time iteration is", exact, &xb, [&](SensRule at) -> int {
+        return at == SensRule::kAfterHessian ? check_rti_handle(h) : MMPC_OK;
+    });
+    if (rc || a.B == 0 || !check_workspace) return rc;
+    return check_rti_workspace(h, a);
+}
+// The one check of a feedback launch's arguments (it has no model inputs, so check_sens_args does not apply).
+int check_rti_feedback_args(mmpc_handle* h, const RtiArgs& a) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (a.B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    if (int rc = check_bounds_stride(h->info, a.bounds_stride)) return rc;
+    if (int rc = check_rti_handle(h)) return rc;
+    if (a.B == 0) return MMPC_OK;
+    if (!a.x0_meas) return fail(MMPC_ERR_INVALID_ARG, "x0_meas is NULL");
+    if (!a.V_inout) return fail(MMPC_ERR_INVALID_ARG, "V_inout is NULL");
+    if (a.B > 0x7fffffffLL) return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit (2^31-1)");
+    return check_rti_workspace(h, a);
+}
+// the three regions of an RTI workspace of B instances: records | undo log | status words
+struct RtiRegions {
+    double *rec, *undo;
+    int32_t* status;
+};
+RtiRegions rti_regions(const mmpc_model_info& mi, int64_t B, void* workspace) {
+    const uint64_t blocks = (static_cast<uint64_t>(B) + 63) / 64;
+    RtiRegions r;
+    r.rec = static_cast<double*>(workspace);
+    r.undo = r.rec + blocks * rti_rec_block_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes);
+    r.status = reinterpret_cast<int32_t*>(r.undo +
+                                          blocks * rti_undo_block_doubles(mi.num_x, mi.num_u, mi.num_shooting_nodes));
+    return r;
+}
+// a preparation whose arguments check_rti_prepare_args has passed, B > 0, device pointers, on the current device: one
+// launch, stream-ordered, no allocation, no synchronisation
+int launch_rti_prepare(mmpc_handle* h, const RtiArgs& a, bool exact) {
+    RtiPrepareXbParams px{};   // fill_sens_params writes the barrier's tail; the kernels take the head alone
+    fill_sens_params(h, a, XbTail{}, px);
+    const RtiRegions r = rti_regions(h->info, a.B, a.workspace);
+    px.status = a.status;
+    px.rec = r.rec;
+    px.ws_status = r.status;
+    const RtiPrepareParams p = px;
+    return with_model(h->info.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        return with_sens_variant<M>(exact, a.u_lb || a.u_ub, false, [&](auto ex, auto bd, auto) -> int {
+            rti_prepare_lane_kernel<M, decltype(ex)::value, decltype(bd)::value><<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
+            MMPC_HIP(hipGetLastError());
+            return MMPC_OK;
+        });
+    });
+}
+// a feedback launch whose arguments check_rti_feedback_args has passed, on the same terms
+int launch_rti_feedback(mmpc_handle* h, const RtiArgs& a) {
+    const RtiRegions r = rti_regions(h->info, a.B, a.workspace);
+    RtiFeedbackParams p{};
+    p.B = a.B;
+    p.N = h->info.num_shooting_nodes;
+    p.x0 = a.x0_meas;
+    p.u_lb = a.u_lb;
+    p.u_ub = a.u_ub;
+    p.b_stride = static_cast<int32_t>(a.bounds_stride);
+    p.V = a.V_inout;
+    p.u0 = a.u0;
+    p.step_inf = a.step_inf;
+    p.status = a.fb_status;
+    p.rec = r.rec;
+    p.undo = r.undo;
+    p.ws_status = r.status;
+    return with_model(h->info.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        return with_sens_variant<M>(false, a.u_lb || a.u_ub, false, [&](auto, auto bd, auto) -> int {
+            rti_feedback_lane_kernel<M::NX, M::NU, decltype(bd)::value><<<grid1d(p.B, 64), 64, 0, a.stream>>>(p);
+            MMPC_HIP(hipGetLastError());
+            return MMPC_OK;
+        });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -2163,6 +2278,81 @@ int mmpc_solve_jvp_batch_host(mmpc_handle* h, int64_t B, const double* V, const 
         if (dV) MMPC_HIP(hipMemcpyAsync(dV, d + off_dV, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
         if (du0) MMPC_HIP(hipMemcpyAsync(du0, d + off_du0, B * nu * sizeof(double), hipMemcpyDeviceToHost, s));
         if (jvp_status) MMPC_HIP(hipMemcpyAsync(jvp_status, a.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MMPC_HIP(hipStreamSynchronize(s));
+        return MMPC_OK;
+    });
+}
+
+int mmpc_rti_workspace_bytes(const mmpc_handle* h, int64_t B, uint64_t* bytes) {
+    if (!h || !bytes || B < 0) return fail(MMPC_ERR_INVALID_ARG, "null argument or B < 0");
+    *bytes = rti_ws_bytes(h->info, B);
+    return MMPC_OK;
+}
+
+int mmpc_rti_prepare_batch(mmpc_handle* h, int64_t B, const double* V, const double* u_prev, const double* traj,
+                           const double* weights, int64_t weights_stride, const double* u_lb, const double* u_ub,
+                           int64_t bounds_stride, int32_t n_pin, int32_t hessian, int32_t* prep_status,
+                           void* workspace, uint64_t workspace_bytes, void* stream) {
+    RtiArgs a;
+    static_cast<SensArgs&>(a) = SensArgs{B, V, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin,
+                                         hessian, prep_status, reinterpret_cast<hipStream_t>(stream)};
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes;
+    bool exact = false;
+    if (int rc = check_rti_prepare_args(h, a, true, &exact)) return rc;
+    if (B == 0) return MMPC_OK;
+    return on_handle_device(h, [&] { return launch_rti_prepare(h, a, exact); });
+}
+
+int mmpc_rti_feedback_batch(mmpc_handle* h, int64_t B, const double* x0_meas, const double* u_lb, const double* u_ub,
+                            int64_t bounds_stride, double* V_inout, double* u0_out, double* step_inf, int32_t* status,
+                            void* workspace, uint64_t workspace_bytes, void* stream) {
+    RtiArgs a;
+    a.B = B, a.u_lb = u_lb, a.u_ub = u_ub, a.bounds_stride = bounds_stride;
+    a.stream = reinterpret_cast<hipStream_t>(stream);
+    a.x0_meas = x0_meas, a.V_inout = V_inout, a.u0 = u0_out, a.step_inf = step_inf, a.fb_status = status;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes;
+    if (int rc = check_rti_feedback_args(h, a)) return rc;
+    if (B == 0) return MMPC_OK;
+    return on_handle_device(h, [&] { return launch_rti_feedback(h, a); });
+}
+
+int mmpc_rti_step_batch_host(mmpc_handle* h, int64_t B, double* V_inout, const double* x0_meas, const double* u_prev,
+                             const double* traj, const double* weights, int64_t weights_stride, const double* u_lb,
+                             const double* u_ub, int64_t bounds_stride, int32_t n_pin, int32_t hessian, double* u0_out,
+                             double* step_inf, int32_t* status) {
+    RtiArgs a;
+    static_cast<SensArgs&>(a) =
+        SensArgs{B, V_inout, u_prev, traj, weights, weights_stride, u_lb, u_ub, bounds_stride, n_pin, hessian};
+    bool exact = false;
+    if (int rc = check_rti_prepare_args(h, a, false, &exact)) return rc;   // before the strides size a copy
+    if (B == 0) return MMPC_OK;
+    if (!x0_meas) return fail(MMPC_ERR_INVALID_ARG, "x0_meas is NULL");
+    std::lock_guard<std::mutex> lk(h->host_mu);
+    return on_handle_device(h, [&]() -> int {
+        const mmpc_model_info& mi = h->info;
+        const size_t nx = mi.num_x, nu = mi.num_u, NV = mi.num_v;
+        const size_t nWs = rti_ws_bytes(mi, B) / sizeof(double);
+        // own regions, after u_ub: x0_meas | u0 | step_inf | the workspace
+        double* d;
+        size_t off_none, off_x0;
+        if (int rc = stage_sens_inputs(h, a, 0, B * nx + B * nu + B + nWs, &d, &off_none, &off_x0)) return rc;
+        const size_t off_u0 = off_x0 + B * nx, off_si = off_u0 + B * nu, off_ws = off_si + B;
+        hipStream_t s = a.stream;
+        MMPC_HIP(hipMemcpyAsync(d + off_x0, x0_meas, B * nx * sizeof(double), hipMemcpyHostToDevice, s));
+        a.x0_meas = d + off_x0;
+        a.V_inout = d;   // the staged V, first in the buffer
+        a.u0 = d + off_u0;
+        a.step_inf = d + off_si;
+        a.fb_status = a.status;
+        a.status = nullptr;   // the feedback launch's status carries the preparation's
+        a.workspace = d + off_ws;
+        a.workspace_bytes = nWs * sizeof(double);
+        if (int rc = launch_rti_prepare(h, a, exact)) return rc;
+        if (int rc = launch_rti_feedback(h, a)) return rc;
+        MMPC_HIP(hipMemcpyAsync(V_inout, d, B * NV * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (u0_out) MMPC_HIP(hipMemcpyAsync(u0_out, d + off_u0, B * nu * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (step_inf) MMPC_HIP(hipMemcpyAsync(step_inf, d + off_si, B * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (status) MMPC_HIP(hipMemcpyAsync(status, a.fb_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         MMPC_HIP(hipStreamSynchronize(s));
         return MMPC_OK;
     });

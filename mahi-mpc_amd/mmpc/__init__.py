@@ -52,6 +52,8 @@ GAIN_OK, GAIN_GAUSS_NEWTON_FALLBACK, GAIN_FAILED = 0, 1, 2
 VJP_OK, VJP_GAUSS_NEWTON_FALLBACK, VJP_FAILED = 0, 1, 2
 # and of the solve JVP (mmpc_solve_jvp_batch)
 JVP_OK, JVP_GAUSS_NEWTON_FALLBACK, JVP_FAILED = 0, 1, 2
+# and of the real-time iteration calls (mmpc_rti_prepare_batch / mmpc_rti_feedback_batch)
+RTI_OK, RTI_GAUSS_NEWTON_FALLBACK, RTI_FAILED = 0, 1, 2
 MODEL_TWO_LINK_ARM, MODEL_EXO_ARM, MODEL_USER = 0, 1, 2
 USER_LIB_DIR = os.path.join(ROOT, "lib", "user")
 BUILTIN_MODELS = ("two_link_arm", "double_pendulum", "exo_arm", "exo")  # "mmpc_model" names libmmpc.so serves   # models generated from SX by ModelGenerator (make -C host user)
@@ -146,6 +148,16 @@ def lib(path: str | None = None):
         L.mmpc_solve_jvp_batch.argtypes = _jvp + [_vp, C.c_uint64, _vp]
         L.mmpc_solve_jvp_batch_host.argtypes = _jvp
         L.mmpc_solve_jvp_workspace_bytes.argtypes = [_vp, C.c_int64, C.POINTER(C.c_uint64)]
+        # real-time iteration.  prepare: (V, u_prev, traj, weights), weights_stride, (u_lb, u_ub), bounds_stride, n_pin,
+        # hessian, prep_status, workspace, workspace_bytes, stream;  feedback: x0_meas, (u_lb, u_ub), bounds_stride,
+        # (V_inout, u0_out, step_inf, status), workspace, workspace_bytes, stream;  host: V_inout, x0_meas, (u_prev, traj,
+        # weights), weights_stride, (u_lb, u_ub), bounds_stride, n_pin, hessian, (u0_out, step_inf, status)
+        L.mmpc_rti_workspace_bytes.argtypes = [_vp, C.c_int64, C.POINTER(C.c_uint64)]
+        L.mmpc_rti_prepare_batch.argtypes = ([_vp, C.c_int64] + [_vp] * 4 + [C.c_int64, _vp, _vp, C.c_int64, C.c_int32,
+                                                                             C.c_int32, _vp, _vp, C.c_uint64, _vp])
+        L.mmpc_rti_feedback_batch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64] + [_vp] * 5 + [C.c_uint64, _vp]
+        L.mmpc_rti_step_batch_host.argtypes = ([_vp, C.c_int64] + [_vp] * 5 + [C.c_int64, _vp, _vp, C.c_int64, C.c_int32,
+                                                                               C.c_int32] + [_vp] * 3)
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -633,6 +645,78 @@ class Solver:
                                                       _ptr(lb), _ptr(ub), bs, int(n_pin), _ptr(dx0), _ptr(du_prev),
                                                       _ptr(dtraj), _ptr(dweights), int(hessian), _ptr(out["dV"]),
                                                       _ptr(out["du0"]), _ptr(out["jvp_status"])))
+        return out
+
+    def rti_workspace_bytes(self, B) -> int:
+        """Bytes of the workspace rti_prepare / rti_feedback of B instances need (mmpc_rti_workspace_bytes):
+        ceil(B / 64) * 64 * ((N K (K + 1) + NV) * 8 + 4), K = nx + nu."""
+        n = C.c_uint64(0)
+        self._check(self._L.mmpc_rti_workspace_bytes(self._h, B, C.byref(n)))
+        return int(n.value)
+
+    def rti_prepare(self, B, V, u_prev, traj, weights, workspace=None, workspace_bytes=None, prep_status=None,
+                    weights_stride=0, u_lb=None, u_ub=None, bounds_stride=0, n_pin=0, hessian=HESSIAN_AUTO,
+                    stream=None):
+        """Preparation of a real-time iteration at the plan V, which need not be a solution (mmpc_rti_prepare_batch;
+        device tensors, one stream-ordered launch): linearisation, gradient, defects and the backward Riccati sweep,
+        stored in the workspace for rti_feedback.  Returns a dict with workspace (a float64 torch tensor on V's device
+        unless given; a raw address needs workspace_bytes) and prep_status [B] int32 (0 as asked, 1 Gauss-Newton
+        fallback, 2 failed)."""
+        if workspace is None or prep_status is None:
+            import torch
+            if workspace is None:
+                workspace = torch.empty((max(self.rti_workspace_bytes(B), 8) // 8,), dtype=torch.float64,
+                                        device=V.device)
+            if prep_status is None:
+                prep_status = torch.empty((B,), dtype=torch.int32, device=V.device)
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else 0
+        self._check(self._L.mmpc_rti_prepare_batch(self._h, B, _ptr(V), _ptr(u_prev), _ptr(traj), _ptr(weights),
+                                                   weights_stride, _ptr(u_lb), _ptr(u_ub), int(bounds_stride),
+                                                   int(n_pin), int(hessian), _ptr(prep_status), _ptr(workspace),
+                                                   int(workspace_bytes), stream))
+        return dict(workspace=workspace, prep_status=prep_status)
+
+    def rti_feedback(self, B, x0_meas, V, workspace, workspace_bytes=None, u0=None, step_inf=None, status=None,
+                     u_lb=None, u_ub=None, bounds_stride=0, stream=None):
+        """Feedback of a real-time iteration (mmpc_rti_feedback_batch; device tensors, one stream-ordered launch, no
+        model inside): V, the plan rti_prepare was given, becomes V + dV in place with V[:, :nx] = x0_meas; u_lb / u_ub
+        clamp the controls.  Returns a dict with V, u0 [B, nu] (the control to apply), step_inf [B] (max |dV|) and
+        status [B] int32 (0 as asked, 1 Gauss-Newton fallback, 2 failed: V unchanged, u0 the plan's own, step_inf
+        inf).  Outputs are torch tensors on V's device unless given (tensors or raw addresses, e.g. of HostBuffer
+        memory, used as given)."""
+        out = dict(u0=u0, step_inf=step_inf, status=status)
+        shapes = dict(u0=(B, self.nu), step_inf=(B,), status=(B,))
+        want = [k for k in out if out[k] is None]
+        if want:
+            import torch
+            for k in want:
+                out[k] = torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float64, device=V.device)
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else 0
+        self._check(self._L.mmpc_rti_feedback_batch(self._h, B, _ptr(x0_meas), _ptr(u_lb), _ptr(u_ub),
+                                                    int(bounds_stride), _ptr(V), _ptr(out["u0"]),
+                                                    _ptr(out["step_inf"]), _ptr(out["status"]), _ptr(workspace),
+                                                    int(workspace_bytes), stream))
+        out["V"] = V
+        return out
+
+    def rti_step_host(self, V, x0_meas, u_prev, traj, weights, u_lb=None, u_ub=None, n_pin=0, hessian=HESSIAN_AUTO):
+        """rti_prepare + rti_feedback for numpy arrays, synchronous (mmpc_rti_step_batch_host; the library brings the
+        workspace); u_lb / u_ub [nu] shared or [B, nu] per instance.  V is not modified; returns a dict of numpy
+        arrays with rti_feedback's keys."""
+        nx, nu, N, NV = self.nx, self.nu, self.N, self.NV
+        V = _f64(V, (-1, NV)).copy()
+        B = V.shape[0]
+        x0_meas, u_prev = _f64(x0_meas, (B, nx)), _f64(u_prev, (B, nu))
+        traj, weights = _f64(traj, (B, N, nx)), _f64(weights)
+        ws = 0 if weights.ndim == 1 else weights.shape[-1]
+        lb, ub, bs = _host_bounds(u_lb, u_ub, B, nu)
+        out = dict(V=V, u0=np.zeros((B, nu)), step_inf=np.zeros(B), status=np.full(B, -1, np.int32))
+        self._check(self._L.mmpc_rti_step_batch_host(self._h, B, _ptr(V), _ptr(x0_meas), _ptr(u_prev), _ptr(traj),
+                                                     _ptr(weights), ws, _ptr(lb), _ptr(ub), bs, int(n_pin),
+                                                     int(hessian), _ptr(out["u0"]), _ptr(out["step_inf"]),
+                                                     _ptr(out["status"])))
         return out
 
     def set_state_bounds(self, x_lb=None, x_ub=None):
