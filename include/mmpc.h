@@ -609,6 +609,27 @@ int mmpc_rti_step_batch_host(mmpc_handle* h, int64_t B, double* V_inout, const d
                              const double* u_ub, int64_t bounds_stride, int32_t n_pin, int32_t hessian, double* u0_out,
                              double* step_inf, int32_t* status);
 
+/* ---- the shift between two ticks of a real-time iteration loop (additive to ABI 6) ----
+ * V_out is V_in moved n = n_shift stages earlier, per instance, K = nx + nu:
+ *   stages k = 0 .. N-n-1 of V_out (x_k, u_k) and the state x_{N-n} are stages k + n of V_in and its x_N, bit for bit;
+ *   every later control is the old u_{N-1}, bit for bit;
+ *   every later state is rolled out, x_{k+1} = F(x_k, u_{N-1}) = x_k + h f(x_k, u_{N-1}): the Euler step of the NLP's
+ *   defects, evaluated by the model's own device function.
+ * u_prev_out [B][nu] (may be NULL) receives the old u_{n-1}, the control in force over the new first interval, which
+ * is the u_prev of a preparation at V_out.  With n = 0 V_out is a copy of V_in and u_prev_out is not written.
+ * V_in and V_out [B][NV] are DEVICE pointers and may not overlap (V_out == V_in is refused; a partial overlap is the
+ * caller's error).  One stream-ordered launch on `stream` that never synchronises, never allocates and uses no
+ * workspace, so it can be captured in a hipGraph.  A non-finite entry propagates into its own row only.
+ * MMPC_ERR_INVALID_ARG: n_shift outside 0 .. N (mmpc_last_error names `n_shift`), a NULL V_in or V_out (named),
+ * V_out == V_in.  MMPC_ERR_UNSUPPORTED: a linear-mode model, as for the entries above.  Everything is checked from the
+ * arguments alone before any device call.  n_shift and the model's mode are properties of the call, not of the data, and
+ * are checked first: B = 0 with a valid n_shift on a nonlinear model is a no-op success whatever the pointers are, B = 0
+ * with a bad n_shift or a linear-mode model is still the error above.  A state-bounded handle is accepted, since the
+ * shifted plan is also the warm start of a solve; the rolled-out states are NOT checked against any state bound and
+ * may lie outside the box. */
+int mmpc_rti_shift_batch(mmpc_handle* h, int64_t B, const double* V_in, int32_t n_shift, double* V_out,
+                         double* u_prev_out, void* stream);
+
 /* ---- feedback gains and solve VJP of a state-bounded handle: the sensitivity barrier (additive to ABI 6) ----
  * A state-bounded solve is an interior-point solve: the V it returns lies strictly inside every bound, near the
  * central path of its last barrier value.  Its sensitivity is the recursion of the two definitions above with the

@@ -1771,6 +1771,45 @@ int launch_rti_feedback(mmpc_handle* h, const RtiArgs& a) {
     });
 }
 
+// The one check of a shift's arguments.  State bounds are not looked at: the shift is also the warm start of a solve.
+int check_rti_shift_args(mmpc_handle* h, int64_t B, const double* V_in, int32_t n_shift, const double* V_out) {
+    if (!h) return fail(MMPC_ERR_INVALID_ARG, "null handle");
+    if (B < 0) return fail(MMPC_ERR_INVALID_ARG, "B < 0");
+    const int N = h->info.num_shooting_nodes;
+    if (n_shift < 0 || n_shift > N)
+        return fail(MMPC_ERR_INVALID_ARG,
+                    "n_shift is " + std::to_string(n_shift) + ": must be 0 .. " + std::to_string(N));
+    if (h->info.is_linear)
+        return fail(MMPC_ERR_UNSUPPORTED, "real-time iteration is not available for a linear-mode model");
+    if (B == 0) return MMPC_OK;
+    if (!V_in) return fail(MMPC_ERR_INVALID_ARG, "V_in is NULL");
+    if (!V_out) return fail(MMPC_ERR_INVALID_ARG, "V_out is NULL");
+    if (V_out == V_in) return fail(MMPC_ERR_INVALID_ARG, "V_out is V_in: the two plans may not overlap");
+    if (rti_shift_copy_blocks(B, h->info.num_v) + rti_shift_roll_blocks(B, n_shift) > 0x7fffffffULL)
+        return fail(MMPC_ERR_INVALID_ARG, "B exceeds the grid limit of the shift (2^31-1 blocks)");
+    return MMPC_OK;
+}
+// a shift whose arguments check_rti_shift_args has passed, B > 0, on the same terms as the launches above
+int launch_rti_shift(mmpc_handle* h, int64_t B, const double* V_in, int32_t n_shift, double* V_out, double* u_prev_out,
+                     hipStream_t stream) {
+    RtiShiftParams p{};
+    p.B = B;
+    p.N = h->info.num_shooting_nodes;
+    p.n = n_shift;
+    p.h = h->info.step_size;
+    p.V_in = V_in;
+    p.V_out = V_out;
+    p.u_prev = n_shift > 0 ? u_prev_out : nullptr;
+    p.copy_blocks = static_cast<uint32_t>(rti_shift_copy_blocks(B, h->info.num_v));
+    const unsigned grid = p.copy_blocks + static_cast<unsigned>(rti_shift_roll_blocks(B, n_shift));
+    return with_model(h->info.model_id, [&](auto* m) {
+        using M = std::remove_pointer_t<decltype(m)>;
+        rti_shift_kernel<M><<<grid, kRtiShiftThreads, 0, stream>>>(p);
+        MMPC_HIP(hipGetLastError());
+        return static_cast<int>(MMPC_OK);
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C-ABI
@@ -2314,6 +2353,15 @@ int mmpc_rti_feedback_batch(mmpc_handle* h, int64_t B, const double* x0_meas, co
     if (int rc = check_rti_feedback_args(h, a)) return rc;
     if (B == 0) return MMPC_OK;
     return on_handle_device(h, [&] { return launch_rti_feedback(h, a); });
+}
+
+int mmpc_rti_shift_batch(mmpc_handle* h, int64_t B, const double* V_in, int32_t n_shift, double* V_out,
+                         double* u_prev_out, void* stream) {
+    if (int rc = check_rti_shift_args(h, B, V_in, n_shift, V_out)) return rc;
+    if (B == 0) return MMPC_OK;
+    return on_handle_device(h, [&] {
+        return launch_rti_shift(h, B, V_in, n_shift, V_out, u_prev_out, reinterpret_cast<hipStream_t>(stream));
+    });
 }
 
 int mmpc_rti_step_batch_host(mmpc_handle* h, int64_t B, double* V_inout, const double* x0_meas, const double* u_prev,

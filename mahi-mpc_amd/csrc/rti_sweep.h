@@ -1,6 +1,7 @@
 // rti_sweep.h -- real-time iteration: one full-step SQP iteration at a plan that is NOT a solution, split into a
 // preparation launch (everything that does not depend on the measured state) and a feedback launch (one forward sweep
 // over stored records, no model inside) (mmpc_rti_prepare_batch / mmpc_rti_feedback_batch, include/mmpc.h).
+// The shift of the plan between two ticks (mmpc_rti_shift_batch) is at the end of the file.
 //
 // The step dV at the plan V^ solves
 //   min 1/2 dV^T H dV + grad J(V^)^T dV   s.t.  dx_{k+1} = A_k dx_k + B_k du_k + c_k,  dx_0 = x0_meas - x^_0,
@@ -323,6 +324,94 @@ __global__ __launch_bounds__(64) void rti_feedback_lane_kernel(const RtiFeedback
     }
     if (p.step_inf) p.step_inf[b] = ok ? smax : INFINITY;
     if (p.status) p.status[b] = st;
+}
+
+// ---- the shift between two ticks (mmpc_rti_shift_batch) ----
+// V_out is V_in moved n stages earlier: entries 0 .. (N - n) K + nx - 1 of a row are entries n K .. of the old row, the
+// later controls are the old u_{N-1}, the later states are rolled out by x_{k+1} = x_k + h f(x_k, u_{N-1}).
+struct RtiShiftParams {
+    int64_t B;
+    int N, n;               // 0 <= n <= N
+    double h;
+    const double* V_in;     // [B][NV]
+    double* V_out;          // [B][NV], no overlap with V_in
+    double* u_prev;         // [B][nu] or null: the old u_{n-1} (n >= 1)
+    uint32_t copy_blocks;   // blocks 0 .. copy_blocks-1 copy, the rest roll out
+};
+constexpr int kRtiShiftThreads = 256, kRtiShiftPerThread = 4;
+// blocks of the copy part (kRtiShiftThreads * kRtiShiftPerThread entries each) and of the roll-out (one lane per
+// instance; none for n = 0)
+inline uint64_t rti_shift_copy_blocks(int64_t B, int64_t NV) {
+    const uint64_t per = kRtiShiftThreads * kRtiShiftPerThread;
+    return (static_cast<uint64_t>(B) * NV + per - 1) / per;
+}
+inline uint64_t rti_shift_roll_blocks(int64_t B, int n) {
+    return n > 0 ? (static_cast<uint64_t>(B) + kRtiShiftThreads - 1) / kRtiShiftThreads : 0;
+}
+
+// One launch, two kinds of block, which write disjoint entries of V_out and read V_in alone, so no order between
+// them is needed.
+// * Copy blocks: the B NV entries of V_out as one flat array, consecutive lanes on consecutive entries, so a wave
+//   reads and writes whole cache lines whatever NV is (one lane per instance would stride by NV).  Each entry is
+//   the old entry n K later in its own row, or the old u_{N-1}'s; the rolled-out states are skipped.  No FP64
+//   arithmetic: the doubles move through registers bit for bit.
+// * Roll-out blocks (n >= 1): one lane per instance, the serial chain of n Euler steps from the old x_N under the
+//   old u_{N-1}, by the model's own device function; it also stores u_prev.  n nx doubles written per instance.
+// A non-finite entry stays in its own row: no lane reads another instance's entries.
+template <class Model>
+__global__ __launch_bounds__(kRtiShiftThreads) void rti_shift_kernel(const RtiShiftParams p) {
+    constexpr int NX = Model::NX, NU = Model::NU, K = NX + NU;
+    const int N = p.N, n = p.n;
+    const uint32_t NV = (uint32_t)NX * (N + 1) + (uint32_t)NU * N;
+    const uint32_t kept = (uint32_t)(N - n) * K + NX;   // entries of a row that are old entries n K later
+    if (blockIdx.x < p.copy_blocks) {
+        const uint64_t total = (uint64_t)p.B * NV;
+        const uint64_t base = (uint64_t)blockIdx.x * (kRtiShiftThreads * kRtiShiftPerThread) + threadIdx.x;
+#pragma unroll
+        for (int e = 0; e < kRtiShiftPerThread; ++e) {
+            const uint64_t i = base + (uint64_t)e * kRtiShiftThreads;
+            if (i >= total) break;
+            uint64_t b;
+            uint32_t j;
+            if (total <= 0xffffffffull) {   // uniform: the 32-bit division is a fraction of the 64-bit one
+                const uint32_t q = (uint32_t)i / NV;
+                b = q;
+                j = (uint32_t)i - q * NV;
+            } else {
+                b = i / NV;
+                j = (uint32_t)(i - b * NV);
+            }
+            const double* const row = p.V_in + b * NV;
+            if (j < kept) {
+                p.V_out[i] = row[j + (uint32_t)n * K];
+            } else {
+                const uint32_t r = (j - kept) % K;   // kept = a stage's x done: r < NU is a control, the rest x
+                if (r < NU) p.V_out[i] = row[(uint32_t)(N - 1) * K + NX + r];
+            }
+        }
+        return;
+    }
+    const int64_t b = (int64_t)(blockIdx.x - p.copy_blocks) * kRtiShiftThreads + threadIdx.x;
+    if (b >= p.B) return;
+    const double* const row = p.V_in + b * NV;
+    double* const out = p.V_out + b * NV;
+    double x[NX], u[NU], xd[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) x[r] = row[(int64_t)N * K + r];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) u[c] = row[(int64_t)(N - 1) * K + NX + c];
+    if (p.u_prev) {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) p.u_prev[b * NU + c] = row[(int64_t)(n - 1) * K + NX + c];
+    }
+    for (int k = N - n + 1; k <= N; ++k) {
+        model_eval<Model>(x, u, xd);
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+            x[r] = x[r] + p.h * xd[r];
+            out[(int64_t)k * K + r] = x[r];
+        }
+    }
 }
 
 }  // namespace mmpc

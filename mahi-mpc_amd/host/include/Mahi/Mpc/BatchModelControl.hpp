@@ -18,6 +18,7 @@
 #pragma once
 #include <atomic>
 #include <condition_variable>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -106,6 +107,35 @@ public:
     // u_min, u_max) with that instance's limits; the plan for a stage without gains or an instance with status 2
     std::vector<double> controls_at_time(mahi::util::Time time, const std::vector<double>& states_measured);
 
+    // Real-time iteration mode (include/mmpc.h, "real-time iteration").  Off by default, and with it off
+    // every code path, buffer and published value is what it is without these members.  With it on, calc_u and the
+    // start_calc worker run one of two ticks:
+    //   * a full tick -- all inputs up, one solve from the resident plan, everything down -- when no preparation
+    //     exists, when the previous tick raised the fallback flag (an instance with status 2 or step_inf >
+    //     step_inf_max; the whole batch re-solves), or when the preparation is stale (made for another instant than
+    //     `time`: round((time - t_prepared) / step) != 0);
+    //   * an RTI tick otherwise: only the measured states go up, one feedback launch runs on the records the
+    //     preparation stored, u_0 is published with the tick's time as soon as that launch is done (u0, step_inf and
+    //     status are written by the kernel into host memory), the whole plan follows on the copy stream.  The
+    //     `controls` argument is not used: the preparation took the plan's own control in force.  An instance with
+    //     status 2 publishes the plan's own u_0.  last_status() of an RTI tick is the step's status (0 as asked, 1
+    //     Gauss-Newton fallback, 2 failed), last_iterations() 1.
+    // After either tick, without waiting, the plan is shifted by one stage on the device (mmpc_rti_shift_batch: the last
+    // control repeated, the terminal state rolled out) and the next preparation is queued at the shifted plan, for
+    // time + step, with the weights and control limits in force now and the targets of set_next_targets (else this
+    // tick's targets moved one row, the last row repeated).  The clamp of a feedback launch is the control box its
+    // preparation ran under.  set_warm_start_shift is not consulted in this mode.
+    // The first tick with the mode on throws for a linear-mode model, any finite state limit,
+    // set_num_control_inputs_saved(m > 0) or set_feedback_stages(n > 0).  set_rti_mode(true) throws for a generated
+    // model library built before the RTI entries existed.  Additive: not part of the reference's interface.
+    void set_rti_mode(bool on, double step_inf_max = std::numeric_limits<double>::infinity());
+    // targets [B*N*nx] of the next preparation (the horizon starting at the next tick); consumed by one tick
+    void set_next_targets(const std::vector<double>& trajs_next);
+    int64_t rti_ticks() const { return m_rti_ticks; }
+    int64_t full_solve_ticks() const { return m_full_ticks; }   // full ticks with the mode on
+    std::vector<double> last_step_inf();                         // [B] max |dV| of the published RTI tick; 0 after a full tick
+    double mean_feedback_latency_ms() const;                     // tick entry -> u_0 published, RTI ticks only
+
 private:
     struct Impl;
     std::unique_ptr<Impl> m;
@@ -139,6 +169,19 @@ private:
 
     std::mutex m_solve_mutex;  // one tick pipeline at a time (calc_u vs the worker)
     double m_tick_ms_sum = 0.0;
+
+    // real-time iteration mode
+    std::atomic<bool> m_rti_mode{false};
+    double m_step_inf_max = std::numeric_limits<double>::infinity();   // under m_solve_mutex
+    std::vector<double> m_next_targets;                                // under m_state_mutex, as m_have_next_targets
+    bool m_have_next_targets = false;
+    std::atomic<int64_t> m_rti_ticks{0}, m_full_ticks{0};
+    double m_fb_ms_sum = 0.0;
+    std::vector<double> m_out_step_inf;   // under m_output_mutex, as the u_0 published ahead of its plan:
+    bool m_u0_ahead = false;              // u_0 of a tick whose plan has not landed yet
+    mahi::util::Time m_u0_time;
+    std::vector<double> m_u0_x, m_u0_u;   // [B nx] measured states, [B nu]
+    void rti_tick(mahi::util::Time time, const double* states, const double* controls, const double* trajs);
 
     void enqueue_tick(int slot, mahi::util::Time time, const double* states, const double* controls,
                       const double* trajs);

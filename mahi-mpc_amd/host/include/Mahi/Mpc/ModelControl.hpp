@@ -3,6 +3,7 @@
 // the MI355X batched SQP behind include/mmpc.h.  casadi::Dict is replaced by mahi::mpc::Dict.
 #pragma once
 #include <atomic>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -21,6 +22,7 @@ namespace mahi {
 namespace mpc {
 namespace detail {
 struct ModelLibrary;
+class RtiPipeline;
 }
 
 using Dict = std::map<std::string, double>;
@@ -96,6 +98,18 @@ public:
     // neighbouring-extremal control.  For a stage without gains (i >= n, or feedback_status() == 2): the plan.
     ControlResult control_at_time(mahi::util::Time time, const std::vector<double>& x_measured);
 
+    // Real-time iteration mode (include/mmpc.h, "real-time iteration"): BatchModelControl's mode for
+    // this one controller, through the same device pipeline with B = 1 -- see BatchModelControl::set_rti_mode for the
+    // tick rule (full tick / RTI tick, fallback flag, stale preparation) and the refusals, which are the same.  The
+    // next preparation's targets are this tick's `traj` moved one row (the last row repeated).  An RTI tick steps the
+    // plan with one feedback launch on the measured state (`control` is not used) and fills control_results from the
+    // stepped plan; last_status() is then the step's status (0 / 1 / 2), last_iterations() 1.  Off by default, and
+    // with it off nothing changes.  Additive: not part of the reference's interface.
+    void set_rti_mode(bool on, double step_inf_max = std::numeric_limits<double>::infinity());
+    long long rti_ticks() const { return m_rti_ticks; }
+    long long full_solve_ticks() const { return m_full_ticks; }   // full ticks with the mode on
+    double last_step_inf();                                        // max |dV| of the last RTI tick; 0 after a full tick
+
     // ---- build extensions (not in the reference) ----
     // solver status of the last calc_u (the reference ignores IPOPT's status, ModelControl.cpp:159-161)
     int last_status() const { return m_last_status; }
@@ -140,6 +154,16 @@ private:
     std::atomic<int> m_feedback_stages{0};
     std::vector<double> m_gains;   // [n][nu][nx + nu] of the published plan (under m_output_mutex, as m_gain_status)
     int m_gain_status = -1;
+
+    std::atomic<bool> m_rti_mode{false};   // real-time iteration mode
+    double m_step_inf_max = std::numeric_limits<double>::infinity();
+    std::shared_ptr<detail::RtiPipeline> m_rti;
+    std::mutex m_rti_mutex;                // calc_u (either mode), set_rti_mode and load_model exclude one another
+    int m_device = -1;                     // the device current when the handle was made: the pipeline's
+    std::atomic<long long> m_rti_ticks{0}, m_full_ticks{0};
+    double m_last_step_inf = 0.0;          // under m_output_mutex
+    void rti_calc_u(mahi::util::Time time, const std::vector<double>& state, const std::vector<double>& control,
+                    const std::vector<double>& traj);
 
     int m_last_status = -1;
     int m_last_iters = 0;

@@ -14,6 +14,7 @@
 
 #include "../../../include/mmpc.h"
 #include "model_library.hpp"
+#include "rti_pipeline.hpp"
 
 namespace mahi {
 namespace mpc {
@@ -64,6 +65,8 @@ struct BatchModelControl::Impl {
     int next_slot = 0;
     bool have_prev = false;
     mahi::util::Time prev_time;
+
+    std::unique_ptr<detail::RtiPipeline> rti;   // real-time iteration mode: allocated at the first set_rti_mode(true)
 
     void check(int rc, const char* what) const { lib->check(rc, what); }
 };
@@ -157,6 +160,7 @@ BatchModelControl::~BatchModelControl() {
     }
     (void)hipFree(m->d_V);
     (void)hipFree(m->d_tmp);
+    m->rti.reset();
     if (m->h) m->lib->destroy(m->h);
     if (m->compute) (void)hipStreamDestroy(m->compute);
     if (m->copy) (void)hipStreamDestroy(m->copy);
@@ -309,12 +313,143 @@ void BatchModelControl::calc_u(mahi::util::Time time, const std::vector<double>&
     if (states.size() != b * m->nx || controls.size() != b * m->nu || trajs.size() != b * m->N * m->nx)
         throw std::invalid_argument("BatchModelControl::calc_u: states/controls/trajs size mismatch");
     std::lock_guard<std::mutex> lg(m_solve_mutex);
+    if (m_rti_mode) return rti_tick(time, states.data(), controls.data(), trajs.data());
     const int slot = m->next_slot;
     m->next_slot ^= 1;
     m->pend_t0[slot] = std::chrono::steady_clock::now();
     enqueue_tick(slot, time, states.data(), controls.data(), trajs.data());
     publish(slot ^ 1);
     publish(slot);
+}
+
+void BatchModelControl::set_rti_mode(bool on, double step_inf_max) {
+    std::lock_guard<std::mutex> lg(m_solve_mutex);   // between ticks
+    Impl& I = *m;
+    HIPC(hipSetDevice(I.dev));
+    publish(I.next_slot);   // nothing of the pipelined path stays in flight across the switch
+    publish(I.next_slot ^ 1);
+    HIPC(hipStreamSynchronize(I.compute));
+    m_step_inf_max = step_inf_max;
+    if (on == m_rti_mode) return;
+    if (on) {
+        if (!I.rti) I.rti.reset(new detail::RtiPipeline(I.lib, I.h, I.B, I.dev));
+        I.rti->set_plan(I.d_V, hipMemcpyDeviceToDevice);   // the warm start goes with the mode
+    } else {
+        I.rti->get_plan(I.d_V, hipMemcpyDeviceToDevice);
+        I.have_prev = false;
+    }
+    m_rti_mode = on;
+}
+
+void BatchModelControl::set_next_targets(const std::vector<double>& trajs_next) {
+    if (trajs_next.size() != static_cast<size_t>(m_B) * m->N * m->nx)
+        throw std::invalid_argument("set_next_targets: trajs_next must have B * num_shooting_nodes * num_x entries");
+    std::lock_guard<std::mutex> lg(m_state_mutex);
+    m_next_targets = trajs_next;
+    m_have_next_targets = true;
+}
+
+std::vector<double> BatchModelControl::last_step_inf() {
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    return m_out_step_inf;
+}
+
+double BatchModelControl::mean_feedback_latency_ms() const { return m_rti_ticks ? m_fb_ms_sum / m_rti_ticks : 0.0; }
+
+// One tick with the mode on (under m_solve_mutex): detail::RtiPipeline decides between a full and an RTI tick.
+void BatchModelControl::rti_tick(mahi::util::Time time, const double* states, const double* controls,
+                                 const double* trajs) {
+    Impl& I = *m;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nx = I.nx, nu = I.nu, b = static_cast<size_t>(I.B);
+    if (model_parameters.is_linear) throw std::runtime_error("real-time iteration mode: not available for a linear-mode model");
+    for (double v : model_parameters.x_min)
+        if (std::isfinite(v)) throw std::runtime_error("real-time iteration mode: not available with finite state limits");
+    for (double v : model_parameters.x_max)
+        if (std::isfinite(v)) throw std::runtime_error("real-time iteration mode: not available with finite state limits");
+    if (m_num_control_inputs_saved.load() > 0)
+        throw std::runtime_error("real-time iteration mode: not available with set_num_control_inputs_saved(m > 0)");
+    if (m_feedback_stages.load() > 0)
+        throw std::runtime_error("real-time iteration mode: not available with set_feedback_stages(n > 0)");
+    std::vector<double> w, lb, ub, next;
+    {
+        std::lock_guard<std::mutex> lg(m_weights_mutex);
+        w.insert(w.end(), m_Q.begin(), m_Q.end());
+        w.insert(w.end(), m_R.begin(), m_R.end());
+        w.insert(w.end(), m_Rm.begin(), m_Rm.end());
+    }
+    bool finite = false, per_instance = false;
+    {
+        // the limits in force now, by the rules of enqueue_tick
+        std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+        per_instance = m_limits_per_instance;
+        if (per_instance) {
+            lb = m_u_min_table;
+            ub = m_u_max_table;
+            for (size_t i = 0; i < b * nu; ++i) finite |= lb[i] > -1e19 || ub[i] < 1e19;
+        } else {
+            lb.resize(nu);
+            ub.resize(nu);
+            for (size_t c = 0; c < nu; ++c) {
+                lb[c] = c < model_parameters.u_min.size() ? model_parameters.u_min[c] : -10e30;
+                ub[c] = c < model_parameters.u_max.size() ? model_parameters.u_max[c] : 10e30;
+                finite |= lb[c] > -1e19 || ub[c] < 1e19;
+            }
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lg(m_state_mutex);
+        if (m_have_next_targets) next.swap(m_next_targets);
+        m_have_next_targets = false;
+    }
+    detail::RtiPipeline::Inputs in;
+    in.t = time.as_seconds();
+    in.states = states;
+    in.controls = controls;
+    in.trajs = trajs;
+    in.next_trajs = next.empty() ? nullptr : next.data();
+    in.weights = w.data();
+    in.lb = finite ? lb.data() : nullptr;
+    in.ub = finite ? ub.data() : nullptr;
+    in.per_instance = per_instance;
+    in.step_inf_max = m_step_inf_max;
+    double u0_ms = 0.0;
+    bool was_rti = false;
+    try {
+        was_rti = I.rti->tick(in, [&] {
+        // u_0 ahead of its plan: control_at_time serves it for the tick's first interval until the plan lands
+        std::lock_guard<std::mutex> lg(m_output_mutex);
+        m_u0_x.assign(states, states + b * nx);
+        m_u0_u.assign(I.rti->u0(), I.rti->u0() + b * nu);
+        m_u0_time = time;
+        m_u0_ahead = true;
+        u0_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        });
+    } catch (...) {   // the plan of that u_0 never lands: control_at_time goes back to the last published plan
+        std::lock_guard<std::mutex> lg(m_output_mutex);
+        m_u0_ahead = false;
+        throw;
+    }
+    {
+        std::lock_guard<std::mutex> lg(m_output_mutex);
+        std::memcpy(m_out_V.data(), I.rti->plan(), b * I.NV * sizeof(double));
+        m_out_status = I.rti->status();
+        m_out_iters = I.rti->iterations();
+        m_out_step_inf.assign(I.rti->step_inf(), I.rti->step_inf() + b);
+        m_out_time = time;
+        m_out_fb = 0;
+        m_out_G.clear();
+        m_out_gst.clear();
+        m_u0_ahead = false;
+    }
+    if (was_rti) {
+        m_fb_ms_sum += u0_ms;
+        ++m_rti_ticks;
+    } else {
+        ++m_full_ticks;
+    }
+    m_tick_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ++m_ticks;
 }
 
 void BatchModelControl::set_state(mahi::util::Time time, const std::vector<double>& states,
@@ -350,6 +485,10 @@ void BatchModelControl::worker() {
             tr = m_trajs;
         }
         std::lock_guard<std::mutex> lg(m_solve_mutex);
+        if (m_rti_mode) {
+            rti_tick(t, s.data(), c.data(), tr.data());
+            continue;
+        }
         const int slot = m->next_slot;
         m->next_slot ^= 1;
         m->pend_t0[slot] = std::chrono::steady_clock::now();
@@ -377,8 +516,14 @@ void BatchModelControl::stop_calc() {
 BatchModelControl::ControlResult BatchModelControl::control_at_time(int64_t b, mahi::util::Time time) {
     if (b < 0 || b >= m_B) throw std::out_of_range("control_at_time: instance index");
     std::lock_guard<std::mutex> lg(m_output_mutex);
-    if (m_ticks == 0) throw std::logic_error("control_at_time before the first solve");
     const size_t nx = m->nx, nu = m->nu, N = m->N;
+    if (m_u0_ahead) {   // an RTI tick's u_0, published before its plan: it serves the tick's first interval
+        const bool first = !(mahi::util::seconds(m_u0_time.as_seconds() + m->step) < time);
+        if (first || m_ticks == 0)
+            return ControlResult(m_u0_time, std::vector<double>(m_u0_x.begin() + b * nx, m_u0_x.begin() + (b + 1) * nx),
+                                 std::vector<double>(m_u0_u.begin() + b * nu, m_u0_u.begin() + (b + 1) * nu));
+    }
+    if (m_ticks == 0) throw std::logic_error("control_at_time before the first solve");
     // ModelControl.cpp:192-197: the last stage whose time is before `time` (the first one if none)
     size_t i = 0;
     while (i < N && mahi::util::seconds(m_out_time.as_seconds() + m->step * i) < time) i++;

@@ -15,6 +15,7 @@
 
 #include "../../../include/mmpc.h"
 #include "model_library.hpp"
+#include "rti_pipeline.hpp"
 
 namespace mahi {
 namespace mpc {
@@ -31,6 +32,7 @@ ModelControl::ModelControl(std::string model_name, std::vector<double> Q, std::v
 ModelControl::~ModelControl() {
     m_stop = true;
     if (m_thread.joinable()) m_thread.join();  // the reference busy-waits on m_done_calcing (:16-19)
+    m_rti.reset();                             // before its handle goes
     if (m_handle) m_backend->destroy(m_handle);
 }
 
@@ -41,6 +43,9 @@ void ModelControl::load_model(const std::string& model_name) {
     std::stringstream ss;
     ss << f.rdbuf();
     model_parameters = model_parameters_from_json_string(ss.str());
+    std::lock_guard<std::mutex> lk(m_rti_mutex);   // not under a running calc_u
+    m_rti.reset();   // the pipeline belongs to the handle: a new model starts with the mode off
+    m_rti_mode = false;
     if (m_handle) m_backend->destroy(m_handle);
     m_handle = nullptr;
     m_backend = ModelLibrary::load(model_parameters, path);
@@ -48,6 +53,9 @@ void ModelControl::load_model(const std::string& model_name) {
     mmpc_model_info info;
     m_backend->check(m_backend->get_model_info(m_handle, &info), "mmpc_get_model_info");
     m_V.assign(static_cast<size_t>(info.num_v), 0.0);  // v_init = 0 (ModelControl.cpp:29-50)
+    // the handle runs on the device that is current when it is used (mmpc_opts.device = -1); the pipeline's buffers
+    // go to the one current now, when the handle is made
+    if (hipGetDevice(&m_device) != hipSuccess) m_device = -1;
 }
 
 std::vector<double> ModelControl::packed_weights() {
@@ -65,10 +73,13 @@ std::vector<double> ModelControl::packed_weights() {
 
 void ModelControl::calc_u(mahi::util::Time control_time, const std::vector<double>& state,
                           const std::vector<double>& control, std::vector<double> traj) {
+    // calc_u, set_rti_mode and load_model exclude one another: the switch never sees m_V under a running solve
+    std::lock_guard<std::mutex> lk(m_rti_mutex);
     curr_time = control_time;
     const size_t nx = model_parameters.num_x, nu = model_parameters.num_u, N = model_parameters.num_shooting_nodes;
     if (state.size() != nx || control.size() != nu || traj.size() != N * nx)
         throw std::invalid_argument("ModelControl::calc_u: state/control/traj size mismatch");
+    if (m_rti_mode) return rti_calc_u(control_time, state, control, traj);
     const std::vector<double> w = packed_weights();
     std::vector<double> lb, ub;
     {
@@ -121,6 +132,70 @@ void ModelControl::calc_u(mahi::util::Time control_time, const std::vector<doubl
                          "mmpc_feedback_gains_batch_host");
     }
     format_outputs(m_V, std::move(gains), gst);  // m_V stays as the next warm start (ModelControl.cpp:160-161)
+}
+
+void ModelControl::set_rti_mode(bool on, double step_inf_max) {
+    std::lock_guard<std::mutex> lg(m_rti_mutex);   // between ticks
+    m_step_inf_max = step_inf_max;
+    if (on == m_rti_mode) return;
+    if (on) {
+        if (!m_rti) {
+            if (m_device < 0) throw std::runtime_error("set_rti_mode: no HIP device");
+            m_rti = std::make_shared<detail::RtiPipeline>(m_backend, m_handle, 1, m_device);
+        }
+        m_rti->set_plan(m_V.data(), hipMemcpyHostToDevice);   // the warm start goes with the mode
+    } else {
+        m_rti->get_plan(m_V.data(), hipMemcpyDeviceToHost);
+    }
+    m_rti_mode = on;
+}
+
+double ModelControl::last_step_inf() {
+    std::lock_guard<std::mutex> lg(m_output_mutex);
+    return m_last_step_inf;
+}
+
+// calc_u with the mode on: one tick of detail::RtiPipeline with B = 1
+void ModelControl::rti_calc_u(mahi::util::Time time, const std::vector<double>& state,
+                              const std::vector<double>& control, const std::vector<double>& traj) {
+    const size_t nu = model_parameters.num_u;
+    if (model_parameters.is_linear)
+        throw std::runtime_error("real-time iteration mode: not available for a linear-mode model");
+    for (const std::vector<double>* v : {&model_parameters.x_min, &model_parameters.x_max})
+        for (double x : *v)
+            if (std::isfinite(x))
+                throw std::runtime_error("real-time iteration mode: not available with finite state limits");
+    if (m_num_control_inputs_saved.load() > 0)
+        throw std::runtime_error("real-time iteration mode: not available with set_num_control_inputs_saved(m > 0)");
+    if (m_feedback_stages.load() > 0)
+        throw std::runtime_error("real-time iteration mode: not available with set_feedback_stages(n > 0)");
+    const std::vector<double> w = packed_weights();
+    std::vector<double> lb, ub;
+    {
+        std::lock_guard<std::mutex> lg(m_control_limits_mutex);
+        lb = model_parameters.u_min;
+        ub = model_parameters.u_max;
+    }
+    detail::RtiPipeline::Inputs in;
+    in.t = time.as_seconds();
+    in.states = state.data();
+    in.controls = control.data();
+    in.trajs = traj.data();
+    in.weights = w.data();
+    in.lb = lb.size() == nu ? lb.data() : nullptr;   // as calc_u hands them to the solve
+    in.ub = ub.size() == nu ? ub.data() : nullptr;
+    in.step_inf_max = m_step_inf_max;
+    const bool was_rti = m_rti->tick(in, [] {});
+    m_V.assign(m_rti->plan(), m_rti->plan() + m_V.size());
+    m_last_status = m_rti->status()[0];
+    m_last_iters = m_rti->iterations()[0];
+    m_last_kkt = 0.0;
+    ++(was_rti ? m_rti_ticks : m_full_ticks);
+    {
+        std::lock_guard<std::mutex> lg(m_output_mutex);
+        m_last_step_inf = m_rti->step_inf()[0];
+    }
+    format_outputs(m_V);
 }
 
 std::vector<std::vector<double>> ModelControl::calc_u_batch(const std::vector<std::vector<double>>& states,

@@ -41,6 +41,14 @@ struct ModelLibrary {
     decltype(&mmpc_sensitivity_barrier_default) sensitivity_barrier_default = &mmpc_sensitivity_barrier_default;
     decltype(&mmpc_set_sensitivity_barrier) set_sensitivity_barrier = &mmpc_set_sensitivity_barrier;
     decltype(&mmpc_last_error) last_error = &mmpc_last_error;
+    // real-time iteration mode (set_rti_mode): null in a generated library built before the entries existed, which
+    // makes set_rti_mode(true) throw
+    decltype(&mmpc_rti_workspace_bytes) rti_workspace_bytes = &mmpc_rti_workspace_bytes;
+    decltype(&mmpc_rti_prepare_batch) rti_prepare_batch = &mmpc_rti_prepare_batch;
+    decltype(&mmpc_rti_feedback_batch) rti_feedback_batch = &mmpc_rti_feedback_batch;
+    decltype(&mmpc_rti_shift_batch) rti_shift_batch = &mmpc_rti_shift_batch;
+    decltype(&mmpc_host_alloc) host_alloc = &mmpc_host_alloc;
+    decltype(&mmpc_host_free) host_free = &mmpc_host_free;
     void* dl = nullptr;  // kept loaded for the process lifetime (HIP code objects), as CasADi keeps its libraries
 
     void check(int rc, const char* what) const {
@@ -51,6 +59,10 @@ struct ModelLibrary {
         void* s = dlsym(dl, name);
         if (!s) throw std::runtime_error(std::string("model library lacks ") + name);
         f = reinterpret_cast<F>(s);
+    }
+    template <class F>
+    void bind_optional(F& f, const char* name) {
+        f = reinterpret_cast<F>(dlsym(dl, name));
     }
     // dll_filepath relative to the JSON's directory first, then to the working directory
     // A generated model names itself in "mmpc_model"; built-in models (and reference-written JSONs, whose
@@ -94,6 +106,12 @@ struct ModelLibrary {
         b->bind(b->sensitivity_barrier_default, "mmpc_sensitivity_barrier_default");
         b->bind(b->set_sensitivity_barrier, "mmpc_set_sensitivity_barrier");
         b->bind(b->last_error, "mmpc_last_error");
+        b->bind_optional(b->rti_workspace_bytes, "mmpc_rti_workspace_bytes");
+        b->bind_optional(b->rti_prepare_batch, "mmpc_rti_prepare_batch");
+        b->bind_optional(b->rti_feedback_batch, "mmpc_rti_feedback_batch");
+        b->bind_optional(b->rti_shift_batch, "mmpc_rti_shift_batch");
+        b->bind_optional(b->host_alloc, "mmpc_host_alloc");
+        b->bind_optional(b->host_free, "mmpc_host_free");
         return b;
     }
 };

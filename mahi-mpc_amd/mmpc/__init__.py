@@ -158,6 +158,8 @@ def lib(path: str | None = None):
         L.mmpc_rti_feedback_batch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64] + [_vp] * 5 + [C.c_uint64, _vp]
         L.mmpc_rti_step_batch_host.argtypes = ([_vp, C.c_int64] + [_vp] * 5 + [C.c_int64, _vp, _vp, C.c_int64, C.c_int32,
                                                                                C.c_int32] + [_vp] * 3)
+        # the shift between two ticks: V_in, n_shift, V_out, u_prev_out, stream
+        L.mmpc_rti_shift_batch.argtypes = [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp]
         L.mmpc_host_alloc.argtypes = [C.c_uint64, C.POINTER(_vp)]
         L.mmpc_host_free.argtypes = [_vp]
         L.mmpc_linearize_batch.argtypes = [_vp, C.c_int64] + [_vp] * 6
@@ -700,6 +702,21 @@ class Solver:
                                                     int(workspace_bytes), stream))
         out["V"] = V
         return out
+
+    def rti_shift(self, B, V_in, n_shift=1, V_out=None, u_prev_out=None, stream=None):
+        """The plans V_in [B, NV] moved n_shift stages earlier (mmpc_rti_shift_batch; device tensors, one stream-ordered
+        launch, no workspace): the tail repeats the old u_{N-1} and rolls the states out with the model's Euler step.
+        V_out may not be V_in.  Returns a dict with V and u_prev [B, nu] (the old u_{n_shift-1}; not written for
+        n_shift = 0): torch tensors on V_in's device unless given (tensors or raw addresses, used as given)."""
+        if V_out is None or u_prev_out is None:
+            import torch
+            if V_out is None:
+                V_out = torch.empty((B, self.NV), dtype=torch.float64, device=V_in.device)
+            if u_prev_out is None:
+                u_prev_out = torch.zeros((B, self.nu), dtype=torch.float64, device=V_in.device)
+        self._check(self._L.mmpc_rti_shift_batch(self._h, B, _ptr(V_in), int(n_shift), _ptr(V_out), _ptr(u_prev_out),
+                                                 stream))
+        return dict(V=V_out, u_prev=u_prev_out)
 
     def rti_step_host(self, V, x0_meas, u_prev, traj, weights, u_lb=None, u_ub=None, n_pin=0, hessian=HESSIAN_AUTO):
         """rti_prepare + rti_feedback for numpy arrays, synchronous (mmpc_rti_step_batch_host; the library brings the

@@ -1,0 +1,237 @@
+"""GPU: real-time iteration as a mode of BatchModelControl and ModelControl (set_rti_mode), driven by
+mahi-mpc_amd/host/examples/rti_control_example.cpp as tests/test_gpu_batch_control.py drives its own example.
+
+The model is libmmpc's built-in 2-link arm at N = 17, 2 ms steps; B = 5 for `batch`, 1 for `single`; 8 ticks.  The
+example prints every tick's inputs (measured state, previous control, targets) and what the controller published.
+Python re-enacts every tick through the C-ABI from those inputs -- a full tick is mmpc_solve_batch_bounds from the
+resident plan, an RTI tick mmpc_rti_feedback_batch on the stored records, and after either mmpc_rti_shift_batch (n = 1)
+and mmpc_rti_prepare_batch at the shifted plan with the targets moved one row -- following the kinds of tick the test
+expects, not the ones the example reports.
+
+1. plain loops, batch and single: tick 0 is a full tick, the others RTI ticks, the counters agree; u_0, plan, status and
+   step_inf of every tick are bit for bit the re-enactment's; on every RTI tick the published x_0 is bit for bit the
+   measured state and (published plan - re-enactment's shifted plan) matches rti_reference.dense_rti_step at
+   1e-10 max(1, max |ref|), the rule of tests/test_gpu_rti.py.
+2. limits, fallback and a stale preparation in one batch run: update_control_limits at +-2, a state jump of 0.5 at tick 3
+   with step_inf_max = 0.25 (the jump alone moves x_0 by 0.5, so step_inf >= 0.5 > 0.25 whatever the loop does), no
+   calc_u at tick 6.  Tick 3 is an RTI tick that raises the flag, tick 4 a full tick whose plan is bit for bit the C-ABI
+   solve warm-started from the shifted plan, tick 5 an RTI tick again, tick 7 (after the skipped one) a full tick; every
+   published control is inside the limits bit for bit; the counters agree.  Every tick is bit for bit the re-enactment.
+3. the four refusals (linear-mode model, a finite state limit, committed controls, feedback stages) throw at the first
+   tick.
+4. mode off, batch and single: bit for bit the C-ABI re-enactment of the path without the mode (one warm-started solve
+   per tick, no shift)."""
+import ctypes as C
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, WEIGHTS_CFG
+from rti_reference import dense_rti_step
+import oracle_lib as oracle
+
+pytestmark = pytest.mark.gpu
+HOST = os.path.join(ROOT, "mahi-mpc_amd", "host")
+USER = os.path.join(ROOT, "mahi-mpc_amd", "lib", "user")
+EXE = os.path.join(HOST, "bin", "rti_control_example")
+PLANT = os.path.join(USER, "nonlinear_double_pendulum_linear_functions.so")
+NAME = "nonlinear_double_pendulum"
+NX, NU, N, H, TICKS = 4, 2, 17, 0.002, 8
+K, NV = NX + NU, NX * (N + 1) + NU * N
+W = np.array(WEIGHTS_CFG)
+TOL = 1e-10
+NUM = {"inf": np.inf, "-inf": -np.inf, "nan": np.nan}
+
+
+def model_dir(tmp_path, tag, **kw):
+    """<name>.json served by libmmpc's built-in 2-link arm, with the plant's external beside it"""
+    import mmpc
+    d = tmp_path / tag
+    d.mkdir()
+    mmpc.write_model_json(str(d / f"{NAME}.json"), NAME, NX, NU, 2000, N, model="two_link_arm", **kw)
+    shutil.copy(PLANT, d / f"{NAME}_linear_functions.so")
+    return str(d / NAME)
+
+
+def run(model, B, mode, *args, expect=0):
+    assert os.path.exists(EXE) and os.path.exists(PLANT), "rti_control_example or the plant's external is not built"
+    r = subprocess.run([EXE, model, str(B), str(TICKS), mode, *map(str, args)], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == expect, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    for l in lines:
+        for k, v in l.items():
+            if isinstance(v, list):
+                l[k] = np.array([NUM.get(x, x) if isinstance(x, str) else x for x in v])
+    return lines
+
+
+def dev(a, dtype=None):
+    import torch
+    return torch.tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64, device="cuda")
+
+
+class Reenact:
+    """the controller's device state, driven through the C-ABI"""
+
+    def __init__(self, mmpc_mod, model, B, bounds):
+        import torch
+        self.t, self.B = torch, B
+        self.s = mmpc_mod.Solver(model + ".json")
+        self.V = torch.zeros((B, NV), dtype=torch.float64, device="cuda")
+        self.up = torch.zeros((B, NU), dtype=torch.float64, device="cuda")
+        self.ws = torch.zeros((self.s.rti_workspace_bytes(B) // 8,), dtype=torch.float64, device="cuda")
+        self.w = dev(W)
+        self.lb, self.ub = (None, None) if bounds is None else (dev(bounds[0]), dev(bounds[1]))
+        self.st = torch.zeros((B,), dtype=torch.int32, device="cuda")
+        self.it = torch.zeros((B,), dtype=torch.int32, device="cuda")
+
+    def full(self, x0, control, traj):
+        s, t = self.s, self.t
+        p = lambda a: None if a is None else C.c_void_p(a.data_ptr())   # noqa: E731
+        x0, control, traj = dev(x0), dev(control), dev(traj)
+        s._check(s._L.mmpc_solve_batch_bounds(s._h, self.B, p(x0), p(control), p(traj), p(self.w), 0, p(self.lb),
+                                              p(self.ub), 0, p(self.V), p(self.st), p(self.it), None, None, None))
+        t.cuda.synchronize()
+        V = self.V.cpu().numpy()
+        return dict(V=V, u0=V[:, NX:K].copy(), step_inf=np.zeros(self.B), status=self.st.cpu().numpy(),
+                    iters=self.it.cpu().numpy())
+
+    def feedback(self, x0):
+        r = self.s.rti_feedback(self.B, dev(x0), self.V, self.ws, u_lb=self.lb, u_ub=self.ub)
+        self.t.cuda.synchronize()
+        return dict(V=self.V.cpu().numpy(), u0=r["u0"].cpu().numpy(), step_inf=r["step_inf"].cpu().numpy(),
+                    status=r["status"].cpu().numpy(), iters=np.ones(self.B, np.int32))
+
+    def background(self, traj):
+        """shift into the other buffer and prepare there: (V^, u_prev, the preparation's targets) as numpy"""
+        r = self.s.rti_shift(self.B, self.V, 1)
+        self.V, self.up = r["V"], r["u_prev"]
+        tr = traj.reshape(self.B, N, NX)
+        nxt = np.concatenate([tr[:, 1:], tr[:, -1:]], axis=1)
+        self.s.rti_prepare(self.B, self.V, self.up, dev(nxt), self.w, workspace=self.ws, u_lb=self.lb, u_ub=self.ub)
+        self.t.cuda.synchronize()
+        return self.V.cpu().numpy(), self.up.cpu().numpy(), nxt
+
+    def close(self):
+        self.s.close()
+
+
+def published(line, single):
+    """(plan entries compared, u0) of a tick's line; `single` publishes the N stages x_k, u_k"""
+    n = N * K if single else NV
+    return line["plan"].reshape(-1, n), line["u0"].reshape(-1, NU)
+
+
+def check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense):
+    """every tick bit for bit the re-enactment's; on RTI ticks x_0 and (dense=True) the step against dense_rti_step"""
+    B = 1 if single else 5
+    ticks = [l for l in lines if "tick" in l]
+    assert [l["kind"] for l in ticks] == kinds, [l["kind"] for l in ticks]
+    r = Reenact(mmpc_mod, model, B, bounds)
+    hat = None
+    worst = 0.0
+    for l, kind in zip(ticks, kinds):
+        if kind == "skipped":
+            continue
+        x0 = l["state"].reshape(B, NX)
+        want = r.full(x0, l["control"].reshape(B, NU), l["traj"].reshape(B, N, NX)) if kind == "full" else r.feedback(x0)
+        plan, u0 = published(l, single)
+        what = f"tick {l['tick']} ({kind})"
+        assert np.array_equal(plan, want["V"][:, :plan.shape[1]]), f"{what}: plan"
+        assert np.array_equal(u0, want["u0"]), f"{what}: u0"
+        assert np.array_equal(l["status"], want["status"]), f"{what}: status {l['status']} {want['status']}"
+        assert np.array_equal(l["step_inf"], want["step_inf"]), f"{what}: step_inf"
+        assert np.array_equal(l["iters"], want["iters"]), f"{what}: iterations"
+        if kind == "rti":
+            assert np.array_equal(plan[:, :NX], x0), f"{what}: the published x_0 is the measured state"
+            if dense:
+                Vh, up, tr = hat
+                for b in range(B):
+                    ref = dense_rti_step(oracle.TWO_LINK, N, H, Vh[b], up[b], tr[b], W, x0[b], True)
+                    err = np.abs((want["V"][b] - Vh[b]) - ref).max()
+                    bound = TOL * max(1.0, np.abs(ref).max())
+                    worst = max(worst, err / bound)
+                    assert err <= bound, (what, b, err, bound)
+        hat = r.background(l["traj"])
+    r.close()
+    if dense:
+        print(f"worst (step - dense reference) / bound over the RTI ticks: {worst:.3e}")
+    return ticks
+
+
+@pytest.mark.parametrize("mode", ["batch", "single"])
+def test_loop_is_the_c_abi_reenactment(mode, mmpc_mod, tmp_path):
+    single = mode == "single"
+    model = model_dir(tmp_path, mode)
+    lines = run(model, 1 if single else 5, mode)
+    # ModelControl hands the model file's +-10e30 to the library as bounds, as its calc_u does
+    bounds = ([-10e30] * NU, [10e30] * NU) if single else None
+    check_loop(mmpc_mod, model, lines, ["full"] + ["rti"] * (TICKS - 1), single, bounds, dense=True)
+    summary = lines[-1]
+    assert summary["rti_ticks"] == TICKS - 1 and summary["full_solve_ticks"] == 1, summary
+
+
+def test_limits_fallback_and_stale_preparation(mmpc_mod, tmp_path):
+    model = model_dir(tmp_path, "events")
+    lines = run(model, 5, "batch", 3, 0.5, 6, "step_inf_max=0.25", "limit=2")
+    kinds = ["full", "rti", "rti", "rti", "full", "rti", "skipped", "full"]
+    ticks = check_loop(mmpc_mod, model, lines, kinds, False, ([-2.0] * NU, [2.0] * NU), dense=False)
+    assert (ticks[3]["step_inf"] > 0.25).all(), "the jump moves x_0 by 0.5: the flag is raised"
+    for i in (1, 2):   # before the jump the steps are far below the threshold: no flag
+        assert (ticks[i]["step_inf"] <= 0.25).all(), (i, ticks[i]["step_inf"])
+    for l in ticks:
+        U = l["plan"].reshape(5, NV)[:, :N * K].reshape(5, N, K)[:, :, NX:]
+        assert ((U >= -2.0) & (U <= 2.0)).all() and (np.abs(l["u0"]) <= 2.0).all(), l["tick"]
+    assert np.array_equal(ticks[6]["plan"], ticks[5]["plan"]), "a skipped tick publishes nothing"
+    summary = lines[-1]
+    assert summary["rti_ticks"] == 4 and summary["full_solve_ticks"] == 3, summary
+
+
+@pytest.mark.parametrize("what", ["linear", "state_limit", "pin", "feedback"])
+def test_refusals_throw_at_the_first_tick(what, tmp_path):
+    kw, args = {}, []
+    if what == "linear":
+        kw = dict(is_linear=True)
+    elif what == "state_limit":
+        kw = dict(x_max=[10e30, 10e30, 50.0, 10e30])
+    else:
+        args = [f"{what}=1"]
+    for mode, B in (("batch", 5), ("single", 1)):
+        lines = run(model_dir(tmp_path, f"{what}_{mode}", **kw), B, mode, *args, expect=3)
+        assert len(lines) == 1 and "real-time iteration mode" in lines[0]["error"], lines
+        word = {"linear": "linear", "state_limit": "state limits", "pin": "set_num_control_inputs_saved",
+                "feedback": "set_feedback_stages"}[what]
+        assert word in lines[0]["error"], lines
+
+
+@pytest.mark.parametrize("mode", ["batch", "single"])
+def test_mode_off_is_the_path_without_the_mode(mode, mmpc_mod, tmp_path):
+    single = mode == "single"
+    B = 1 if single else 5
+    model = model_dir(tmp_path, "off_" + mode)
+    lines = run(model, B, mode, "rti=0", "limit=2")
+    ticks = [l for l in lines if "tick" in l]
+    assert [l["kind"] for l in ticks] == ["off"] * TICKS
+    lb, ub = np.full(NU, -2.0), np.full(NU, 2.0)
+    s = mmpc_mod.Solver(model + ".json")
+    r = Reenact(mmpc_mod, model, B, (lb, ub))
+    V = np.zeros((B, NV))
+    for l in ticks:
+        x0, up, tr = l["state"].reshape(B, NX), l["control"].reshape(B, NU), l["traj"].reshape(B, N, NX)
+        if single:   # ModelControl::calc_u: the host entry
+            g = s.solve_batch_host(x0, up, tr, W, V=V, u_lb=lb, u_ub=ub)
+            V, st, it = g["V"], g["status"], g["iters"]
+        else:        # BatchModelControl: the device entry on the resident plan
+            g = r.full(x0, up, tr)
+            V, st, it = g["V"], g["status"], g["iters"]
+        plan, u0 = published(l, single)
+        assert np.array_equal(plan, V[:, :plan.shape[1]]), f"tick {l['tick']}: plan"
+        assert np.array_equal(u0, V[:, NX:K]) and np.array_equal(l["status"], st) and np.array_equal(l["iters"], it)
+    r.close()
+    s.close()
+    assert lines[-1]["rti_ticks"] == 0 and lines[-1]["full_solve_ticks"] == 0
