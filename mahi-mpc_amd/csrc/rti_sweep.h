@@ -194,6 +194,9 @@ __global__ __launch_bounds__(64) void rti_prepare_lane_kernel(const RtiPreparePa
 // multiply-adds before its first use.  160 doubles (320 of the 512 registers a one-wave workgroup can have) are the
 // budget: D = 3 for the 2-link arm (K = 6), 4 for K <= 5, 1 for the exo (K = 12, one record is 156 doubles), where the
 // rows [G | kff] of the next stage are asked for while [A | B | c] of this one are multiplied, and no earlier.
+// A model whose one slot is over the budget still gets D = 1 (mass_chain, K = 16: 272 + 16 = 288 doubles).  The
+// unbounded kernel then takes 256 + 23 registers and no scratch -- the rows of a record are loaded as the sweep consumes
+// them, the slot never stands in registers whole -- and the bounded one spills 175 registers to 632 B of scratch.
 __host__ __device__ constexpr int rti_ring_slots(int nx, int nu) {
     const int per = rti_rec_doubles(nx, nu) + nx + nu, d = 160 / per;
     return d < 1 ? 1 : (d > 4 ? 4 : d);

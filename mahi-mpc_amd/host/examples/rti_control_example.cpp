@@ -14,6 +14,8 @@
 //   pin=<m>            set_num_control_inputs_saved(m)      } with the mode on the first tick throws: the message is
 //   feedback=<n>       set_feedback_stages(n)               } printed as {"error": ...} and the exit code is 3
 //   quiet=1            no line per tick
+//   glitch=<tick>      at that tick entry 0 of the measured state of instance B / 2 handed to calc_u is NaN (a sensor
+//                      glitch); the printed state is the measured one, the plant's own state is untouched
 // One JSON line per tick: the tick's inputs (state, control, traj), its kind ("full", "rti", "off" or "skipped"), u0,
 // step_inf, status, iters and the plan ([B][NV]; `single`: the N published stages x_k, u_k); then one summary line
 // with the counters, mean_tick_ms, mean_feedback_latency_ms (`batch`) and the tracking cost
@@ -70,7 +72,7 @@ int main(int argc, char** argv) {
     const int ticks = std::atoi(argv[3]);
     const bool single = !std::strcmp(argv[4], "single");
     double step_inf_max = std::numeric_limits<double>::infinity(), limit = 0.0, jump_size = 0.0;
-    int jump_tick = -1, skip_tick = -1, pin = 0, feedback = 0, npos = 0;
+    int jump_tick = -1, skip_tick = -1, glitch_tick = -1, pin = 0, feedback = 0, npos = 0;
     bool rti = true, quiet = false;
     for (int i = 5; i < argc; ++i) {
         const char* eq = std::strchr(argv[i], '=');
@@ -88,6 +90,7 @@ int main(int argc, char** argv) {
         else if (key == "pin") pin = std::atoi(eq + 1);
         else if (key == "feedback") feedback = std::atoi(eq + 1);
         else if (key == "quiet") quiet = std::atoi(eq + 1) != 0;
+        else if (key == "glitch") glitch_tick = std::atoi(eq + 1);
         else {
             std::fprintf(stderr, "unknown option %s\n", argv[i]);
             return 2;
@@ -136,9 +139,11 @@ int main(int argc, char** argv) {
                 }
             const char* kind = "skipped";
             const std::vector<double> control_in = control;
+            std::vector<double> measured = state;   // what the controller sees; the plant keeps `state`
+            if (tick == glitch_tick) measured[(B / 2) * nx] = std::numeric_limits<double>::quiet_NaN();
             if (tick != skip_tick) {
-                if (single) mc->calc_u(mahi::util::seconds(t), state, control, tr);
-                else bc->calc_u(mahi::util::seconds(t), state, control, tr);
+                if (single) mc->calc_u(mahi::util::seconds(t), measured, control, tr);
+                else bc->calc_u(mahi::util::seconds(t), measured, control, tr);
                 const long long r = single ? mc->rti_ticks() : bc->rti_ticks();
                 const long long f = single ? mc->full_solve_ticks() : bc->full_solve_ticks();
                 kind = r > n_rti ? "rti" : (f > n_full ? "full" : "off");
@@ -167,7 +172,7 @@ int main(int argc, char** argv) {
             }
             if (!quiet) {
                 std::printf("{\"tick\":%d,\"t\":%.17g,\"kind\":\"%s\"", tick, t, kind);
-                print_array("state", state);
+                print_array("state", measured);
                 print_array("control", control_in);
                 print_array("traj", tr);
                 print_array("u0", control);

@@ -10,7 +10,9 @@ H = L_VV of jvp_reference._lagrangian on stage_data of tests/sens_reference.py.
   with the gradient of the objective itself, so no multiplier convention enters.  The unclamped reference.
 * riccati_rti_step: the recursion of the header, term for term, and its forward sweep, with the clamp of the control
   box when clamp=True.  The reference where a clamp acts.
-* shift_plan / plant_step: what a controller does between two ticks, for the tests that need it."""
+* shift_plan / plant_step: what a controller does between two ticks, for the tests that need it.
+* exact_qp_ratio: the sign that decides between status 0 and the Gauss-Newton fallback's 1; overflow_growth /
+  first_nonfinite_stage: how far the forward sweep grows dx_0, for the tests that make it overflow."""
 import numpy as np
 
 import oracle_lib as oracle
@@ -98,6 +100,7 @@ def riccati_rti_step(model, N, h, V, up, tr, w, x0_meas, exact, lb=None, ub=None
     P = np.zeros((K, K))
     p = np.zeros(K)
     G, kff = np.zeros((N, nu, K)), np.zeros((N, nu))
+    min_ratio = np.inf
     for k in range(N - 1, -1, -1):
         C = np.block([[A[k], B[k]], [np.zeros((nu, nx)), np.eye(nu)]])
         S = blocks[k].copy()   # S_k (+ W_k): the stage block without its Delta-u and Rm terms
@@ -116,6 +119,8 @@ def riccati_rti_step(model, N, h, V, up, tr, w, x0_meas, exact, lb=None, ub=None
             Muu[i, i] = 1.0
             Mus[i, :] = 0.0
             q[nx + i] = 0.0
+        ev = np.linalg.eigvalsh(0.5 * (Muu + Muu.T))
+        min_ratio = min(min_ratio, ev.min() / np.abs(ev).max())
         G[k] = -np.linalg.solve(Muu, Mus)
         kff[k] = np.linalg.solve(Muu, q[nx:])
         G[k][held[k]] = 0.0
@@ -150,7 +155,39 @@ def riccati_rti_step(model, N, h, V, up, tr, w, x0_meas, exact, lb=None, ub=None
     if info is not None:
         info["clamped"] = clamped
         info["V_new"] = Vn
+        info["min_ratio"] = min_ratio
     return dV
+
+
+def exact_qp_ratio(model, N, h, V, up, tr, w, lb=None, ub=None, n_pin=0):
+    """the smallest over the stages of (smallest / largest-magnitude eigenvalue of M_uu) of the exact-Hessian recursion,
+    held rows replaced by the identity: positive exactly when every pivot of the exact sweep is, i.e. when the exact QP
+    is positive definite on the free controls, which is what decides between status 0 and the fallback's 1"""
+    info = {}
+    riccati_rti_step(model, N, h, V, up, tr, w, V[:oracle.DIMS[model][0]], True, lb, ub, n_pin, False, info)
+    return info["min_ratio"]
+
+
+def overflow_growth(model, N, h, V, up, tr, w, exact, lb=None, ub=None, clamp=False, big=1e300):
+    """g = max |dV| / big of the reference step at x0_meas = x^_0 + big on every entry (big = 1e300: nothing
+    overflows, and the step is linear in dx_0 up to 1e-300).  With g >= 1.2 the same sweep at dx_0 = 1.7e308 passes
+    DBL_MAX = 1.797e308 by 13 % or more, whatever the order of its sums: the step must be reported as failed."""
+    nx, _ = oracle.DIMS[model]
+    dV = riccati_rti_step(model, N, h, V, up, tr, w, V[:nx] + big, exact, lb, ub, 0, clamp)
+    assert np.isfinite(dV).all()
+    return np.abs(dV).max() / big
+
+
+def first_nonfinite_stage(model, N, h, V, up, tr, w, exact, lb=None, ub=None, clamp=False, big=1.7e308):
+    """the first stage k at which (du_k, dx_{k+1}) of the reference's forward sweep at x0_meas = big is not finite"""
+    nx, nu = oracle.DIMS[model]
+    K = nx + nu
+    with np.errstate(all="ignore"):
+        dV = riccati_rti_step(model, N, h, V, up, tr, w, np.full(nx, big), exact, lb, ub, 0, clamp)
+    for k in range(N):
+        if not np.isfinite(dV[k * K + nx:(k + 1) * K + nx]).all():
+            return k
+    return None
 
 
 def _row(a, b, shared_ndim):

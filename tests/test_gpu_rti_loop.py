@@ -17,9 +17,14 @@ expects, not the ones the example reports.
    calc_u at tick 6.  Tick 3 is an RTI tick that raises the flag, tick 4 a full tick whose plan is bit for bit the C-ABI
    solve warm-started from the shifted plan, tick 5 an RTI tick again, tick 7 (after the skipped one) a full tick; every
    published control is inside the limits bit for bit; the counters agree.  Every tick is bit for bit the re-enactment.
-3. the four refusals (linear-mode model, a finite state limit, committed controls, feedback stages) throw at the first
+3. a glitched measurement (glitch=2: entry 0 of the measured state of instance B / 2 is NaN at tick 2), batch and
+   single: the instance reports status 2 with step_inf inf and keeps its plan and u_0 bit for bit (the re-enactment's
+   shifted plan), the others status 0; tick 3 is a full tick (RtiPipeline::tick falls back after status 2) whose plan is
+   bit for bit the C-ABI solve warm-started from the re-enactment's shifted plan; 6 RTI and 2 full ticks; every tick
+   is bit for bit the re-enactment.
+4. the four refusals (linear-mode model, a finite state limit, committed controls, feedback stages) throw at the first
    tick.
-4. mode off, batch and single: bit for bit the C-ABI re-enactment of the path without the mode (one warm-started solve
+5. mode off, batch and single: bit for bit the C-ABI re-enactment of the path without the mode (one warm-started solve
    per tick, no shift)."""
 import ctypes as C
 import json
@@ -127,8 +132,10 @@ def published(line, single):
     return line["plan"].reshape(-1, n), line["u0"].reshape(-1, NU)
 
 
-def check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense):
-    """every tick bit for bit the re-enactment's; on RTI ticks x_0 and (dense=True) the step against dense_rti_step"""
+def check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense, hats=None):
+    """every tick bit for bit the re-enactment's; on RTI ticks x_0 (of the instances with status 0: a failed instance
+    keeps its plan) and (dense=True) the step against dense_rti_step.  hats: a list that receives, per tick, the
+    re-enactment's (V^, u_prev, targets) the tick started from (None before the first)"""
     B = 1 if single else 5
     ticks = [l for l in lines if "tick" in l]
     assert [l["kind"] for l in ticks] == kinds, [l["kind"] for l in ticks]
@@ -139,6 +146,8 @@ def check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense):
         if kind == "skipped":
             continue
         x0 = l["state"].reshape(B, NX)
+        if hats is not None:
+            hats.append(hat)
         want = r.full(x0, l["control"].reshape(B, NU), l["traj"].reshape(B, N, NX)) if kind == "full" else r.feedback(x0)
         plan, u0 = published(l, single)
         what = f"tick {l['tick']} ({kind})"
@@ -148,7 +157,8 @@ def check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense):
         assert np.array_equal(l["step_inf"], want["step_inf"]), f"{what}: step_inf"
         assert np.array_equal(l["iters"], want["iters"]), f"{what}: iterations"
         if kind == "rti":
-            assert np.array_equal(plan[:, :NX], x0), f"{what}: the published x_0 is the measured state"
+            ok = want["status"] == 0
+            assert np.array_equal(plan[ok, :NX], x0[ok]), f"{what}: the published x_0 is the measured state"
             if dense:
                 Vh, up, tr = hat
                 for b in range(B):
@@ -190,6 +200,36 @@ def test_limits_fallback_and_stale_preparation(mmpc_mod, tmp_path):
     assert np.array_equal(ticks[6]["plan"], ticks[5]["plan"]), "a skipped tick publishes nothing"
     summary = lines[-1]
     assert summary["rti_ticks"] == 4 and summary["full_solve_ticks"] == 3, summary
+
+
+@pytest.mark.parametrize("mode", ["batch", "single"])
+def test_a_glitched_measurement_fails_alone_and_the_next_tick_is_a_full_solve(mode, mmpc_mod, tmp_path):
+    single = mode == "single"
+    B = 1 if single else 5
+    bad, tick = B // 2, 2
+    model = model_dir(tmp_path, "glitch_" + mode)
+    lines = run(model, B, mode, f"glitch={tick}")
+    kinds = ["full", "rti", "rti", "full", "rti", "rti", "rti", "rti"]
+    bounds = ([-10e30] * NU, [10e30] * NU) if single else None
+    hats = []
+    # every tick bit for bit the re-enactment's: tick 3 is the C-ABI solve warm-started from the re-enactment's shifted
+    # plan of the failed tick
+    ticks = check_loop(mmpc_mod, model, lines, kinds, single, bounds, dense=False, hats=hats)
+    summary = lines[-1]
+    assert summary["rti_ticks"] == 6 and summary["full_solve_ticks"] == 2, summary
+    l = ticks[tick]
+    state = l["state"].reshape(B, NX)
+    assert np.isnan(state[bad, 0]) and np.isfinite(np.delete(state.ravel(), bad * NX)).all(), "the glitch as printed"
+    for t in ticks:
+        assert t is l or np.isfinite(t["state"]).all(), "the plant's own state is untouched"
+    others = np.arange(B) != bad
+    assert l["status"][bad] == 2 and (l["status"][others] == 0).all(), l["status"]
+    assert np.isinf(l["step_inf"][bad]) and np.isfinite(l["step_inf"][others]).all()
+    plan, u0 = published(l, single)
+    Vh = hats[tick][0]   # the shifted plan the preparation ran at: V is untouched, u_0 the plan's own
+    assert np.array_equal(plan[bad], Vh[bad, :plan.shape[1]]) and np.array_equal(u0[bad], Vh[bad, NX:K])
+    assert np.array_equal(ticks[tick + 1]["control"].reshape(B, NU)[bad], Vh[bad, NX:K]), "the plant ran under that u_0"
+    assert (ticks[tick + 1]["status"] == 0).all() and (ticks[tick + 1]["step_inf"] == 0.0).all()
 
 
 @pytest.mark.parametrize("what", ["linear", "state_limit", "pin", "feedback"])

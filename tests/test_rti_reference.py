@@ -25,16 +25,43 @@ standard normal from default_rng(SEED + 101 N + b).
    The error stops falling after n* = 3 steps (2 for two of the five), at <= 6.7e-12 -- the oracle's own convergence
    at 1e-11 / 1e-12, not the step -- and every step before that contracts by at least 130 (quadratically: 130, then
    3e6).  No instance needed a smaller delta than 1e-2.  N_STAR and ERR_REACHED below are these two numbers; the GPU
-   test of the Newton iteration (tests/test_gpu_rti.py) takes its step count and its bound from them."""
+   test of the Newton iteration (tests/test_gpu_rti.py) takes its step count and its bound from them.
+4. the generated models: every zoo case of tests/test_gpu_rti_edges.py (ZOO_FREE, ZOO_CLAMPED) at the oracle's plan of
+   tests/test_user_model_sens_reference.py shifted by one stage, x0_meas as the GPU module draws it: recursion against
+   the dense KKT solve at 1e-10 max(1, max |ref|), both Hessians (measured <= 1.7e-12, cart_pole (33, 65)); the step
+   does not vanish (max |dV| >= 2.9e-2); the exact QP is positive definite on every instance, the M_uu eigenvalue ratio
+   of exact_qp_ratio at least 0.54.  The two ubound cases: the clamp tests' tight box (tight_box) acts on 16 and 7 of
+   37 instances.  The shapes that module has no seed for, cart_pole (4, 5) (6, 5) (7, 5), take seed 0, the first at
+   which the oracle converges on every instance (ZOO_SEEDS).
+5. the growth g = overflow_growth of the forward sweep (the reference step at x^_0 + 1e300, over 1e300), instance 0,
+   exact Hessian: 2-link N = 17 2.2410 (clamped at +-2: 1.3330), exo N = 7 1.4137, 2-link N = 5 1.0100.  The first three
+   are >= 1.2, so at x0_meas = 1.7e308 the sweep passes DBL_MAX by 13 % or more; the reference's own sweep there is
+   first non-finite at stage 3, 4 and 2: after the plan's first stages have been overwritten.  The undo-log test of
+   tests/test_gpu_rti_edges.py rests on this."""
 import numpy as np
 import pytest
 
 import oracle_lib as oracle
-from rti_reference import dense_rti_step, riccati_rti_step, shift_plan
+import test_user_model_sens_reference as zoo
+from rti_reference import (dense_rti_step, exact_qp_ratio, first_nonfinite_stage, overflow_growth, riccati_rti_step,
+                           riccati_rti_step_batch, shift_plan)
 from sens_reference import _jac, held_mask
-from test_solve_vjp_reference import CASES, SEED, H, W_2L, solved
+from test_solve_vjp_reference import CASES, PM2, SEED, H, W_2L, solved
 
 TOL = 1e-10
+# 4. the zoo's cases of tests/test_gpu_rti_edges.py.  The shapes tests/test_user_model_sens_reference.py has no seed
+# for take the first seed from 0 at which the oracle converges on every instance (its rule; asserted below)
+ZOO_SEEDS = {("free", "cart_pole", 4, 5): 0, ("free", "cart_pole", 6, 5): 0, ("free", "cart_pole", 7, 5): 0}
+ZOO_FREE = ([("free", "cart_pole", N, B) for (N, B) in [(1, 5), (2, 3), (3, 9), (33, 65), (4, 5), (6, 5), (7, 5)]]
+            + [("free", model, N, B) for model in ("motor_pendulum", "unicycle") for (N, B) in [(1, 5), (3, 9), (17, 37)]]
+            + [("free", "mass_chain", 1, 5), ("free", "mass_chain", 5, 9)])
+ZOO_CLAMPED = [("ubound", "cart_pole", 17, 37), ("ubound", "unicycle", 17, 37)]
+# 5. name: (model, N, bounds of the plan, clamp, relied on by the GPU's undo-log test, g as measured)
+G_MIN = 1.2
+GROWTH = {"2-link N=17": (oracle.TWO_LINK, 17, PM2, False, True, 2.24),
+          "2-link N=17 clamped": (oracle.TWO_LINK, 17, PM2, True, True, 1.33),
+          "exo N=7": (oracle.EXO, 7, None, False, True, 1.41),
+          "2-link N=5": (oracle.TWO_LINK, 5, None, False, False, 1.010)}
 N_STAR = 3              # steps after which the error of the iterated reference step stops falling (item 3)
 ERR_REACHED = 6.8e-12   # the error it reaches, all five instances
 CONTRACTION = 10.0      # what every step before n* must contract by at |delta|_inf = 1e-2
@@ -153,3 +180,95 @@ def test_iterated_step_is_newtons_method():
     for b in range(errs.shape[0]):
         ratios = errs[b, :n_star[b]] / errs[b, 1:n_star[b] + 1]
         assert (ratios[:-1] >= CONTRACTION).all() and ratios[0] >= CONTRACTION, (b, ratios)
+
+
+# ---------------------------------------------------------------- 4. the generated models (the zoo)
+def zoo_seed(case):
+    return ZOO_SEEDS[case] if case in ZOO_SEEDS else zoo.SEEDS[case]
+
+
+def zoo_shifted(case):
+    """(model id, w, lb, ub, V^ [B, NV], u_prev [B, nu], traj, x0_meas [B, nx]) of a zoo case at the oracle's plans
+    shifted by one stage; x0_meas as tests/test_gpu_rti.py draws it"""
+    _, model, N, B = case
+    nx, nu = zoo.DIMS[model]
+    x0, up, tr, o = zoo.solved(case, zoo_seed(case))
+    assert (o["status"] == 0).all(), "the oracle must converge on every instance"
+    mid = zoo.use(model)
+    rows = [shift_plan(mid, N, zoo.H, o["V"][b]) for b in range(B)]
+    Vh, uph = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+    x0m = Vh[:, :nx] + 1e-2 * np.random.default_rng(SEED + 13 * N + B).standard_normal((B, nx))
+    lb, ub, _, _ = zoo.case_bounds(case)
+    return mid, zoo.weights(nx, nu), lb, ub, Vh, uph, tr, x0m
+
+
+def tight_box(lb, ub, Uh, free_dU):
+    """the per-instance box of the clamp tests: around the plan's own controls [B, N, nu], half of the largest free
+    step wide, intersected with (lb, ub) [nu]; a side of (lb, ub) that is no bound (|.| >= 1e19) stays as it is"""
+    half = 0.5 * np.abs(free_dU).max(axis=(1, 2))[:, None]
+    tl, tu = np.maximum(lb[None, :], Uh.min(1) - half), np.minimum(ub[None, :], Uh.max(1) + half)
+    return np.where(np.abs(lb) < 1e19, tl, lb[None, :]), np.where(np.abs(ub) < 1e19, tu, ub[None, :])
+
+
+@pytest.mark.parametrize("case", ZOO_FREE + ZOO_CLAMPED, ids=zoo._id)
+def test_zoo_recursion_matches_the_dense_kkt_solve(case):
+    kind, model, N, B = case
+    nx, nu = zoo.DIMS[model]
+    mid, w, lb, ub, Vh, up, tr, x0m = zoo_shifted(case)
+    worst, big, ratios = 0.0, 0.0, []
+    for b in range(B):
+        ratios.append(exact_qp_ratio(mid, N, zoo.H, Vh[b], up[b], tr[b], w, lb, ub))
+        for exact in (True, False):
+            d = dense_rti_step(mid, N, zoo.H, Vh[b], up[b], tr[b], w, x0m[b], exact, lb, ub)
+            r = riccati_rti_step(mid, N, zoo.H, Vh[b], up[b], tr[b], w, x0m[b], exact, lb, ub)
+            err, scale = np.abs(d - r).max(), max(1.0, np.abs(d).max())
+            worst, big = max(worst, err / scale), max(big, np.abs(d).max())
+            assert err <= TOL * scale, (b, exact, err)
+    print(f"{zoo._id(case)} seed {zoo_seed(case)}: recursion against dense {worst:.3e}, max |dV| {big:.3e}, exact M_uu "
+          f"eigenvalue ratio {min(ratios):.3e} .. {max(ratios):.3e}, {sum(r <= 0 for r in ratios)} instances not definite")
+    assert big > 1e-3, "the shifted plan is no solution: the step must not vanish"
+    assert min(abs(r) for r in ratios) > 1e-9, "status 0 or 1 must not hang on rounding"
+    if kind != "ubound":
+        return
+    # the clamp tests' tight box: it must act on some instances' free controls and not on all of them
+    K = nx + nu
+    Uh = Vh[:, :-nx].reshape(B, N, K)[:, :, nx:]
+    for exact in (True, False):
+        free, _, _ = riccati_rti_step_batch(mid, N, zoo.H, Vh, up, tr, w, x0m, exact, lb, ub)
+        tl, tu = tight_box(lb, ub, Uh, free[:, :-nx].reshape(B, N, K)[:, :, nx:])
+        held = np.stack([held_mask(mid, N, Vh[b], tl[b], tu[b], 0) for b in range(B)])
+        _, _, clamped = riccati_rti_step_batch(mid, N, zoo.H, Vh, up, tr, w, x0m, exact, tl, tu, clamp=True)
+        acts = np.array([clamped[b][~held[b]].any() for b in range(B)])
+        print(f"{zoo._id(case)} exact={exact}: the tight box acts on {int(acts.sum())} of {B} instances")
+        assert acts.any() and not acts.all()
+
+
+def test_new_zoo_seeds_are_the_first_at_which_the_oracle_converges():
+    for case, seed in ZOO_SEEDS.items():
+        for s in range(seed + 1):
+            conv = bool((zoo.solved(case, s)[3]["status"] == 0).all())
+            assert conv == (s == seed), (case, s, conv)
+
+
+# ---------------------------------------------------------------- 5. the growth that makes 1.7e308 overflow
+def growth_case(name):
+    """(the arguments of overflow_growth after h, as a tuple) of a GROWTH case, instance 0, exact Hessian"""
+    model, N, bounds, clamp = GROWTH[name][:4]
+    w, lb, ub, Vh, up, tr, _ = shifted(model, N, 0, bounds)
+    if not clamp:
+        lb = ub = None
+    return (model, N, H, Vh, up, tr, w, True, lb, ub, clamp)
+
+
+@pytest.mark.parametrize("name", GROWTH)
+def test_growth_of_the_forward_sweep(name):
+    """g of rti_reference.overflow_growth and the first stage at which the sweep at x0_meas = 1.7e308 is not finite;
+    the undo-log test of tests/test_gpu_rti_edges.py relies on g >= 1.2 for the cases marked so"""
+    args = growth_case(name)
+    g, k = overflow_growth(*args), first_nonfinite_stage(*args)
+    print(f"{name}: g = {g:.4f}, first non-finite stage at 1.7e308: {k}")
+    relied_on, recorded = GROWTH[name][4:]
+    assert abs(g - recorded) <= 0.01 * recorded, "the recorded value is the measured one"
+    if relied_on:
+        assert g >= G_MIN
+        assert k is not None and k >= 1, "the plan has been overwritten when the overflow shows"
